@@ -14,6 +14,7 @@ seq_len=200 / hidden=128 / batch=4096 per GPU; per-GPU work is fixed as N grows 
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
   python bench.py --mode ae                                 (the AE step alone: one train_recon_x iteration, 2*B sequences)
+  python bench.py --dump-outputs DIR                        (also writes what the last timed step computed: DIR/<name>.npy)
 
 Prints ONE JSON line on rank 0.  The `roofline` object is measured live in this process with HIP
 events on the launch stream around every launch of the dominant kernel (an instrumented pass of the
@@ -172,7 +173,45 @@ def parse():
                     "(the host's own cost per step) for `config.host_only` (0: skip)")
     ap.add_argument("--config5_steps", type=int, default=2, help="default line only: steps of BASELINE configs[4]'s single-GPU shape "
                     "(2 M items per domain, L=400, d=256, H=8, k=1024, B=4096) timed for the `config5` object (0: skip)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its losses, the parameters it left "
+                         "behind) to DIR/<name>.npy, at most 64 MB in all (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES = 64 << 20          # --dump-outputs writes at most this much
+DUMP_WHOLE = 1 << 20           # elements an array may have and still be written whole
+
+
+def dump_outputs(path, names, out, G, D):
+    """--dump-outputs DIR: what the last timed step computed, as a caller of the step receives it -- the losses it returns (`names`)
+    and the parameters of G and D it updated in place -- one DIR/<name>.npy per array: float32 for tensors, float64 for Python
+    floats.  A parameter larger than the per-array cap (DUMP_WHOLE elements, lowered until the whole dump fits DUMP_BYTES; at the
+    bench shape only the two item tables) is written as DIR/<name>.sample.npy: its elements at sorted flat indices drawn without
+    replacement by numpy's PCG64 seeded with 0, the same indices in every run of the same shape.  The step's inputs depend on the
+    arguments alone (seeded synthetic users, torch.manual_seed(0) before the weights, ops.manual_seed for dropout), so two builds run
+    with the same arguments can be compared array by array."""
+    import numpy as np
+    arrays = list(zip(names, out)) + [("%s.%s" % (pre, n), p.detach()) for pre, m in (("G", G), ("D", D)) if m is not None
+                                       for n, p in m.named_parameters()]
+    numel = [v.numel() if torch.is_tensor(v) else 1 for _, v in arrays]
+    cap = DUMP_WHOLE
+    while cap > 1 and 4 * sum(min(n, cap) for n in numel) > DUMP_BYTES - (1 << 20):     # (1 MB for the .npy headers)
+        cap //= 2
+    os.makedirs(path, exist_ok=True)
+    for (name, v), n in zip(arrays, numel):
+        if not torch.is_tensor(v):
+            a = np.asarray(v, dtype=np.float64)
+        elif n > cap:
+            idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(n, cap, replace=False))
+            a = v.reshape(-1)[torch.from_numpy(idx).to(v.device)].float().cpu().numpy()
+            name += ".sample"
+        else:
+            a = v.float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def make_loaders(args, device, rank, min_len):
@@ -573,6 +612,9 @@ def main():
 
     dt, t_host, out = timed(step, args.warmup, args.steps, dp, device)
     losses = [float(x) for x in out]
+    names = ("recon_a", "recon_b") if ae else ("D_cost", "Wasserstein_D", "g_dis", "recon_a", "recon_b")
+    if args.dump_outputs and rank == 0:        # before anything below runs the step again (the parameters are the last timed step's)
+        dump_outputs(args.dump_outputs, names, out, G, None if ae else D)
 
     # N > 1: what the gradient exchange of ONE step moved and what it cost the compute stream (every rank takes part)
     exchange = None
@@ -668,7 +710,6 @@ def main():
 
     if rank == 0:
         B = args.batch
-        names = ("recon_a", "recon_b") if ae else ("D_cost", "Wasserstein_D", "g_dis", "recon_a", "recon_b")
         line = {
             "metric": "user-sequences/sec (%s step)" % ("AE" if ae else "AE+GAN"),
             "value": round(per_step * args.steps / dt, 1),

@@ -38,12 +38,16 @@ MASK_FILL = -1e9    # GURU/Transformer/transformer.py:123
 # elementary blocks
 # ----------------------------------------------------------------------------------------------
 def positional_table(max_len, d_model, dtype=torch.float32):
-    """Fixed sinusoid table.  GURU/Transformer/transformer.py:95-101 (built in fp32 there)."""
+    """Fixed sinusoid table.  GURU/Transformer/transformer.py:95-101 (built in fp32 there).  Same fp32 steps, but exp / sin / cos
+    are evaluated in float64 and rounded to fp32: torch's fp32 forms differ in the last bit between CPU code paths (MKL picks its
+    kernels by CPU), and one ulp of div_term becomes one ulp of an angle position * div_term -- 4.8e-7 in the first rows of the
+    table, against tests/golden's capture.  Rounded from float64, the table is the same on every host."""
     pe = torch.zeros(max_len, d_model)
     position = torch.arange(0., max_len).unsqueeze(1)
-    div_term = torch.exp(torch.arange(0., d_model, 2) * -(math.log(10000.0) / d_model))
-    pe[:, 0::2] = torch.sin(position * div_term)
-    pe[:, 1::2] = torch.cos(position * div_term)
+    div_term = torch.exp((torch.arange(0., d_model, 2) * -(math.log(10000.0) / d_model)).double()).float()
+    angle = position * div_term
+    pe[:, 0::2] = torch.sin(angle.double()).float()
+    pe[:, 1::2] = torch.cos(angle.double()).float()
     return pe.to(dtype)
 
 

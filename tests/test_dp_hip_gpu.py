@@ -24,6 +24,10 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 NOISE = ("dec_enc_attn.WQ", "dec_enc_attn.WK", "WK.bias")
+# At most 6 processes may hold a GPU at once on a test machine.  This process holds it (the tests before this one ran on it), so
+# a test starts at most 4 rank processes that open one: 5 in all, one to spare.  World sizes above 4 are covered on the CPU
+# (tests/test_dp_gloo.py: W = 8 against the oracle's full batch).
+MAX_GPU_RANKS = 4
 
 
 def _free_port():
@@ -35,6 +39,7 @@ def _free_port():
 
 
 def _run_ranks(argv, world=2, backend="gloo", extra_env=None, timeout=900):
+    assert world <= MAX_GPU_RANKS, "%d rank processes would hold the GPU next to this one (at most %d)" % (world, MAX_GPU_RANKS)
     port = _free_port()
     procs = []
     for rank in range(world):
@@ -117,13 +122,13 @@ def test_dp2_hip_bench_shape(tier, tmp_path, capsys):
     assert _compare_grads(got, gD, gG, 1e-3 if tier == "bf16" else 1e-4, 1e-4 if tier == "bf16" else 2e-5) > 40
 
 
-@pytest.mark.parametrize("world,what,tier", [(4, "case1", "f32"), (8, "bench", "bf16"), (8, "bench", "f32")])
+@pytest.mark.parametrize("world,what,tier", [(4, "case1", "f32"), (4, "bench", "bf16"), (4, "bench", "f32")])
 def test_dp_hip_at_the_metrics_world_sizes(world, what, tier, tmp_path, capsys):
-    """SURVEY 8e asks for W in {2, 4, 8}; BASELINE.json's metric names 8.  A 1-GPU box holds 8 rank PROCESSES (gloo, all on GPU 0):
-    the golden case split 4 x 1 user, the bench shape (B = 16) split 8 x 2 users -- rank::8 sharding, the global mask count with
-    shards of very different live-position counts, the 1 / 8 pre-division of the W-loss and gradient penalty, begin_sync's
-    asynchronous exchange of the two 51 MB table gradients among 8 ranks and the flat bucket -- summed gradients equal the
-    single-process full batch's."""
+    """SURVEY 8e asks for W in {2, 4, 8}; BASELINE.json's metric names 8.  One GPU holds MAX_GPU_RANKS = 4 rank PROCESSES next to this
+    one (gloo, all on GPU 0): the golden case split 4 x 1 user, the bench shape (B = 16) split 4 x 4 users -- rank::4 sharding, the
+    global mask count with shards of very different live-position counts, the 1 / 4 pre-division of the W-loss and gradient penalty,
+    begin_sync's asynchronous exchange of the two 51 MB table gradients among 4 ranks and the flat bucket -- summed gradients equal the
+    single-process full batch's.  W = 8 is held on the CPU (tests/test_dp_gloo.py)."""
     from dp_worker import run_steps
     out = os.path.join(str(tmp_path), "rank0.npz")
     _run_ranks(["grads", what, out], world=world, extra_env={"RG_DP_TIER": tier}, timeout=1500)
@@ -148,17 +153,18 @@ def test_dp_hip_at_the_metrics_world_sizes(world, what, tier, tmp_path, capsys):
     assert _compare_grads(got, gD, gG, 1e-3 if bf else 1e-4, 1e-4 if bf else 2e-5) > 40
 
 
-def test_dp8_hip_loss_curve_equals_single_rank(tmp_path, capsys):
-    """The 20-step phase-1 + 3-iteration phase-2 curve of the loss-curve fixture (B = 16) with EIGHT ranks of two users each against
-    one rank, f32 tier, dropout 0 -- same bounds as the two-rank test below (and the same caveat about phase 2's branches)."""
+def test_dp4_hip_loss_curve_equals_single_rank(tmp_path, capsys):
+    """The 20-step phase-1 + 3-iteration phase-2 curve of the loss-curve fixture (B = 16) with FOUR ranks of four users each (the
+    most one GPU holds here, MAX_GPU_RANKS) against one rank, f32 tier, dropout 0 -- same bounds as the two-rank test below (and the
+    same caveat about phase 2's branches)."""
     from dp_worker import run_curve
     out = os.path.join(str(tmp_path), "curve.npz")
-    _run_ranks(["curve", "curves1", out], world=8, timeout=1500)
+    _run_ranks(["curve", "curves1", out], world=4, timeout=1500)
     got = dict(np.load(out))
     p1, p2, keep = run_curve(load_case("curves1"), 0, 1, None)
     _reset_ops()
     with capsys.disabled():
-        print("\n[DP x8 vs 1 rank, f32 tier] phase-1 max rel diff %.3g | phase-2 max abs diff %s"
+        print("\n[DP x4 vs 1 rank, f32 tier] phase-1 max rel diff %.3g | phase-2 max abs diff %s"
               % (float(np.abs(got["p1"] / p1 - 1).max()), np.array2string(np.abs(got["p2"] - p2).max(0), precision=2)))
     np.testing.assert_allclose(got["p1"], p1, rtol=2e-5, atol=1e-6)
     np.testing.assert_allclose(got["p2"][:, 3:], p2[:, 3:], rtol=1e-4, atol=1e-6)
@@ -253,13 +259,15 @@ def _two_gpus():
 
 
 def test_dp2_rccl_matches_full_batch(tmp_path):
-    """backend="nccl" (RCCL over xGMI), one GPU per rank."""
-    if not _two_gpus():
-        pytest.skip("needs two GPUs")
+    """backend="nccl" (RCCL over xGMI), one GPU per rank.  RCCL refuses two ranks on one device ("Duplicate GPU detected"), so on a
+    1-GPU box the same two rank processes share GPU 0 over gloo, as test_bench_self_launch_two_ranks does; the exchange record says
+    which backend the collectives went through."""
     from dp_worker import run_steps
+    backend = "nccl" if _two_gpus() else "gloo"
     out = os.path.join(str(tmp_path), "rank0.npz")
-    _run_ranks(["grads", "bench", out], backend="nccl", extra_env={"RG_DP_TIER": "bf16"})
+    _run_ranks(["grads", "bench", out], backend=backend, extra_env={"RG_DP_TIER": "bf16"})
     got = dict(np.load(out))
+    assert got["exchange_backend"].item() == backend and int(got["exchange_world"]) == 2
     os.environ["RG_DP_TIER"] = "bf16"
     try:
         gD, gG, sc = run_steps("bench", 0, 1, None)
@@ -303,18 +311,20 @@ def test_bench_self_launch_two_ranks():
     assert line["tiers"]["bf16x3"]["value"] > 0 and line["tiers"]["f32"]["value"] > 0
 
 
-def test_bench_self_launch_eight_ranks():
-    """`python bench.py --gpus 8` -- the command the driver's scaling run issues -- on a 1-GPU box in its gloo-on-one-GPU form, B = 64
-    per rank: one JSON line, n_gpus = 8, 12 * 64 * 8 sequences per step, and the `exchange` record shows EIGHT ranks in the collective
-    with the step's 5 discriminator buckets + the generator's gradients (both 51 MB tables, at --items 100000) handed to all-reduce."""
-    env = {} if _gpus() >= 8 else {"RG_BENCH_SINGLE_DEVICE": "1", "RG_BENCH_BACKEND": "gloo"}
-    line = _bench(["--gpus", "8", "--batch", "64", "--items", "100000", "--steps", "2", "--warmup", "1", "--no_cpu_baseline",
+def test_bench_self_launch_four_ranks():
+    """`python bench.py --gpus 4` -- the widest self-launch one GPU holds here (MAX_GPU_RANKS rank processes next to this one) -- in its
+    gloo-on-one-GPU form, B = 64 per rank: one JSON line, n_gpus = 4, 12 * 64 * 4 sequences per step, and the `exchange` record shows FOUR
+    ranks in the collective with the step's 5 discriminator buckets + the generator's gradients (both 51 MB tables, at --items 100000)
+    handed to all-reduce."""
+    n = MAX_GPU_RANKS
+    env = {} if _gpus() >= n else {"RG_BENCH_SINGLE_DEVICE": "1", "RG_BENCH_BACKEND": "gloo"}
+    line = _bench(["--gpus", str(n), "--batch", "64", "--items", "100000", "--steps", "2", "--warmup", "1", "--no_cpu_baseline",
                    "--batches_per_domain", "1", "--tier_steps", "0", "--ae_steps", "0", "--full_length_steps", "0", "--host_only_steps", "0"],
                   env, timeout=2400)
-    assert line["n_gpus"] == 8 and line["config"]["parallelism"] == "dp8" and line["value"] > 0
-    assert line["config"]["sequences_per_step"] == 12 * 64 * 8
+    assert line["n_gpus"] == n and line["config"]["parallelism"] == "dp%d" % n and line["value"] > 0
+    assert line["config"]["sequences_per_step"] == 12 * 64 * n
     ex = line["exchange"]
-    assert ex["collective_world"] == 8 and ex["backend"] == ("nccl" if _gpus() >= 8 else "gloo")
+    assert ex["collective_world"] == n and ex["backend"] == ("nccl" if _gpus() >= n else "gloo")
     d, dis = 128, 5 * 128
     n_d = (d * dis + dis) + (dis * 2 * dis + 2 * dis) + (2 * dis * dis + dis) + (dis + 1)
     n_tables = 2 * 100002 * 128

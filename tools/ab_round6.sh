@@ -44,7 +44,7 @@ embed)
   tools/embed_ladder_probe > $O/embed_ladder.txt 2> $O/embed_ladder.err; cat $O/embed_ladder.txt | cut -c1-200
   ab_bench shipped ""; RG_EMBED_ROWS=1 ab_bench rows_form ""
   python tools/kb_embed_c5.py > $O/kb_embed_c5.txt 2>&1; RG_EMBED_ROWS=1 python tools/kb_embed_c5.py > $O/kb_embed_c5_rows.txt 2>&1; grep -h embed_pe $O/kb_embed_c5*.txt | cut -c1-220
-  timeout 2400 python -m pytest tests/test_dp_hip_gpu.py -q -x -p no:cacheprovider -k "world_sizes or dp8 or eight" -s > $O/tests_dp8.log 2>&1; tail -12 $O/tests_dp8.log | cut -c1-300
+  timeout 2400 python -m pytest tests/test_dp_hip_gpu.py -q -x -p no:cacheprovider -k "world_sizes or dp4 or four_ranks" -s > $O/tests_dp4.log 2>&1; tail -12 $O/tests_dp4.log | cut -c1-300
   ;;
 embed2)
   # the position-major embedding kernel (PE row in registers, nontemporal stores) against the old forms: stand-alone and in the step

@@ -2,7 +2,7 @@
 # Round 6: everything profiles/r06/ holds, in one GPU-box call:  bash tools/profile_round6.sh
 # New against tools/profile_round5.sh: the tuned peaks probe runs FIRST and its result is what every bench line of this call prices
 # `roofline.achievable` against (same box); the embedding ladder, the FFN-shape probe, the single-query micro-benchmark of the f32-storage
-# tiers; `bench.py --gpus 8` in its gloo-on-one-GPU form; a `train_gan.py --profile` sample.  Counter passes never share a run with a trace
+# tiers; `bench.py --gpus 4` in its gloo-on-one-GPU form; a `train_gan.py --profile` sample.  Counter passes never share a run with a trace
 # domain; the program itself stands behind `--`.
 RD=r06
 cd /tmp && export TMPDIR=/tmp
@@ -53,8 +53,9 @@ timeout 300 python3 tools/kb_lastq.py bf16x3 > $O/kb_lastq_bf16x3.txt 2>&1
 timeout 300 python3 tools/kb_lastq.py bf16 > $O/kb_lastq_bf16.txt 2>&1
 for t in bf16 bf16x3; do timeout 300 python3 tools/kb_post_attn.py $t > $O/kb_post_attn_$t.txt 2>&1; done
 timeout 300 python3 tools/kb_attn_hm.py > $O/kb_attn_hm.txt 2>&1
-# `bench.py --gpus 8` as the driver's scaling run issues it, in the form a 1-GPU box can hold: eight rank processes on GPU 0 over gloo
-RG_BENCH_SINGLE_DEVICE=1 RG_BENCH_BACKEND=gloo timeout 1200 python3 bench.py --gpus 8 --batch 64 --steps 2 --warmup 1 --no_cpu_baseline --batches_per_domain 1 --tier_steps 0 --ae_steps 0 --full_length_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_dp8_gloo_on_one_gpu.json
+# the self-launched multi-rank bench line in the form a 1-GPU box can hold: four rank processes on GPU 0 over gloo (at most 6 processes may
+# hold the GPU at once; profiles/r06/bench_dp8_gloo_on_one_gpu.json was recorded with eight, before that limit)
+RG_BENCH_SINGLE_DEVICE=1 RG_BENCH_BACKEND=gloo timeout 1200 python3 bench.py --gpus 4 --batch 64 --steps 2 --warmup 1 --no_cpu_baseline --batches_per_domain 1 --tier_steps 0 --ae_steps 0 --full_length_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_dp4_gloo_on_one_gpu.json
 # the entry script's own per-kernel tables
 rm -rf /tmp/rg_prof_res && timeout 900 python3 train_gan.py --cross True --synthetic 8192 --seq_len 200 --d_model 128 --n_head 4 --batch_size 4096 --batch_size_val 256 --vocab_size_a 100000 --vocab_size_b 100000 --n_negs 30 --phase1_steps 5 --steps_tune 10 --result_path /tmp/rg_prof_res --profile $O/train_gan_profile --profile_steps 3 > $O/train_gan_profile.log 2>&1
 # ---- config-5 (2 M items, L = 400, d = 256, k = 1024) at B = 4096: with the fused d_model = 256 forward block and without
