@@ -427,6 +427,35 @@ int rg_item_loss_train_supported(int k, int d);
 int rg_item_loss_train(const rg_item_loss_args* args /* host */, float* coef, int dtype, void* stream);
 int rg_item_loss_scatter_binned(const rg_item_loss_args* args /* host */, const float* coef, long long table_rows,
                                 void* workspace, size_t workspace_bytes, int dtype, void* stream);
+/* ---- full-catalogue softmax cross-entropy (decoder_neg=False: GURU/AutoEnc4Rec.py:228-230 ties the logits to the item table,
+ * GURU/AutoEnc4Rec_cross.py:76-78,216-220 uses projection_{a|b}; loss train_auto.py:44-51 / tools/utils.py:77-84 with neg_sample=False
+ * and a 1-D label, quirk Q15).  loss = sum_t m_t (lse_t - z_t[label_t]) / sums[1] with z_t = W h_t over all C rows of W; the
+ * [n, C] logits are never stored.  Only the 16-row tiles of the live list are computed (rg_live_tiles over mask); no float atomics
+ * (deterministic in both libraries).
+ *   rg_full_ce_fwd    train = 0: lse [n] and sums[0] = sum m (lse - z[label]) (per-workgroup partials, reduced in a fixed order);
+ *                     train = 1: also dh = (sum_c softmax_c W_c - W_label) m / sums[1] (the gradient for an upstream gradient of 1;
+ *                     rows of padded tiles -- no mask != 0 -- are written as zeros).  sums[1] = the mask count ON ENTRY (all-reduced under data parallelism).
+ *   rg_full_ce_dw     dw [C, d] f32 += gout[0] / sums[1] * sum_t m_t (softmax_t - onehot(label_t)) h_t^T, lse from rg_full_ce_fwd;
+ *                     every row written once by one workgroup (no atomics).  gout NULL = 1.
+ * dtype RG_BF16 (h, w bf16) or RG_X3 (h, w f32, split bf16 operands: the bf16x3 AND the f32 tier); d in {64, 128, 256};
+ * any C < 2^31 (tails handled).  partials: >= ceil(n / 16) floats of scratch.  Labels outside [0, C) are taken as 0 by both kernels (W is never read out of bounds). */
+typedef struct {
+  const void* h;              /* [n, d] */
+  const void* w;              /* [C, d] */
+  const int64_t* labels;      /* [n] */
+  const float* mask;          /* [n] */
+  const int* live16;          /* rg_live_tiles(mask, n) */
+  float* lse;                 /* [n] out of fwd, in to dw */
+  void* dh;                   /* [n, d] training form (every row written) */
+  float* partials;            /* [ceil(n / 16)] scratch of fwd */
+  float* sums;                /* [2] */
+  const float* gout;          /* [1] dw */
+  float* dw;                  /* [C, d] f32 */
+  long long n; long long C; int d;
+} rg_full_ce_args;
+int rg_full_ce_supported(int d, int dtype);
+int rg_full_ce_fwd(const rg_full_ce_args* args /* host */, int train, int dtype, void* stream);
+int rg_full_ce_dw(const rg_full_ce_args* args /* host */, int dtype, void* stream);
 /* nn.MSELoss()(a, b) (the overlapped-user term of the generator update, GURU/gan_training.py:28-35,:494-507) and its gradient
  * in one pass: out[0] += mean((a - b)^2); da = 2 (a - b) / n = -db for an upstream gradient of 1 (either may be NULL).
  * a, b, da, db: [n] of dtype, n % 8 == 0. */

@@ -15,6 +15,7 @@ import sys
 import torch
 
 from . import ops, profiling
+from .models import check_recon_handle
 from .optim import Adam
 from .training import _extend_result, _new_result, plot
 
@@ -32,10 +33,11 @@ def get_next_batch(data_batch, device):
 
 
 def loss_ae(model, enc_in, dec_in, dec_out, n_items, neg_sample, bs, sl, param_config, mask):
-    """train_auto.py:29-54: SampledCrossEntropyLoss with label 0 over MyRec(recon=True), masked mean."""
-    if not neg_sample:
-        raise NotImplementedError("full-vocabulary softmax (neg_sample=False) is outside the hot path")
-    return _unwrap(model)(enc_in, dec_in, dec_out, n_items, recon=True).loss(mask)
+    """train_auto.py:29-54: SampledCrossEntropyLoss over MyRec(recon=True), masked mean: label 0 over the 1 + n_negs sampled logits,
+    or (neg_sample=False) label dec_out over the whole catalogue (quirk Q15)."""
+    logits = _unwrap(model)(enc_in, dec_in, dec_out, n_items, recon=True)
+    return check_recon_handle(logits, neg_sample).loss(mask)
+
 
 
 def loss_bpr_func(model_train, enc_in, dec_in, dec_out, n_items, mask):

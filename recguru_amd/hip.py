@@ -99,7 +99,8 @@ SYMBOLS = ["rg_last_error", "rg_version", "rg_gemm_nt", "rg_gemm_tn", "rg_attn_f
            "rg_attn_lastq_x_supported", "rg_attn_lastq_x_fwd", "rg_attn_lastq_x_bwd", "rg_attn_lastq_xf_fwd", "rg_attn_lastq_xf_bwd",
            "rg_embed_scatter_binned_workspace", "rg_embed_scatter_bwd_binned", "rg_embed_pe_fwd_split", "rg_mse",
            "rg_dropout_gelu", "rg_add_drop_ln", "rg_cross_add_ln", "rg_embed_pe_fwd2",
-           "rg_det_enabled", "rg_det_set_arenas", "rg_det_fault"]
+           "rg_det_enabled", "rg_det_set_arenas", "rg_det_fault",
+           "rg_full_ce_supported", "rg_full_ce_fwd", "rg_full_ce_dw"]
 LOSS_SAMPLED_CE, LOSS_BPR, LOSS_BPR_SAS = 0, 1, 2
 c_ll = ctypes.c_longlong
 
@@ -983,6 +984,47 @@ def item_loss_scatter_binned(h, table_rows, pos, neg, mask, k, coef, gout, dE, s
                                              dt_of(h), _stream()), "rg_item_loss_scatter_binned")
 
 
+class FullCeArgs(ctypes.Structure):
+    _fields_ = [("h", c_p), ("w", c_p), ("labels", c_p), ("mask", c_p), ("live16", c_p), ("lse", c_p), ("dh", c_p),
+                ("partials", c_p), ("sums", c_p), ("gout", c_p), ("dw", c_p), ("n", c_ll), ("C", c_ll), ("d", c_i)]
+
+
+def _full_ce_code(h):
+    """bf16 tensors: RG_BF16; f32 tensors (the f32, bf16x3 and mixed tiers): RG_X3 -- the f32 tier takes the split-operand form too
+    (~16 significant bits per operand, f32 accumulation and softmax), which meets the north-star tolerance; there is no exact-f32 form."""
+    return BF16 if h.dtype == torch.bfloat16 else X3
+
+
+def full_ce_supported(d, h):
+    return bool(lib().rg_full_ce_supported(int(d), _full_ce_code(h)))
+
+
+def full_ce_fwd(h, w, labels, mask, live, sums, train=True):
+    """Full-catalogue softmax CE over h [n,d] @ w[C,d].T (rg_full_ce_fwd): sums[1] holds the mask count on entry, sums[0] receives
+    sum m (lse - z[label]).  Returns (lse [n] f32, dh [n,d] for an upstream gradient of 1 | None); the kernel writes rows of padded
+    16-row tiles of dh as zeros, their lse is not written.  live: live_tiles(mask, n)."""
+    n, d = h.shape
+    assert h.is_contiguous() and w.is_contiguous() and w.dtype == h.dtype and w.shape[1] == d
+    assert labels.dtype == torch.int64 and labels.numel() == n and mask.dtype == torch.float32 and mask.numel() == n
+    lse = torch.empty(n, device=h.device, dtype=torch.float32)
+    dh = torch.empty_like(h) if train else None
+    partials = torch.empty((n + 15) // 16, device=h.device, dtype=torch.float32)
+    a = FullCeArgs(_p(h), _p(w), _p(labels), _p(mask), _p(live), _p(lse), _p(dh), _p(partials), _p(sums), None, None,
+                   n, w.shape[0], d)
+    _check(lib().rg_full_ce_fwd(ctypes.byref(a), int(bool(train)), _full_ce_code(h), _stream()), "rg_full_ce_fwd")
+    return lse, dh
+
+
+def full_ce_dw(h, w, labels, mask, live, lse, sums, gout, dw):
+    """dw [C,d] f32 += gout / sums[1] * sum_t m_t (softmax_t - onehot(label_t)) h_t (rg_full_ce_dw; lse from full_ce_fwd)."""
+    n, d = h.shape
+    assert dw.dtype == torch.float32 and dw.is_contiguous() and tuple(dw.shape) == tuple(w.shape)
+    a = FullCeArgs(_p(h), _p(w), _p(labels), _p(mask), _p(live), _p(lse), None, None, _p(sums), _p(gout), _p(dw),
+                   n, w.shape[0], d)
+    _check(lib().rg_full_ce_dw(ctypes.byref(a), _full_ce_code(h), _stream()), "rg_full_ce_dw")
+    return dw
+
+
 def mse(a, b, want_grads=True):
     """mean((a - b)^2) as a [1] f32 device tensor and (da, db) for an upstream gradient of 1 (rg_mse)."""
     assert a.shape == b.shape and a.dtype == b.dtype and a.is_contiguous() and b.is_contiguous() and a.numel() % 8 == 0
@@ -1512,7 +1554,30 @@ def _work_ln_bwd(dy, y, rstd, *a, **k):
     return "ln_bwd_kernel", 0.0, 3 * M * N * _esize(dy) + M * 4
 
 
-_WORK = {"attn_out_bwd": _work_attn_out_bwd, "ln_bwd": _work_ln_bwd, "gemm_tn_layer": _work_gemm_tn_layer, "item_loss_scatter_binned": _work_item_loss_scatter, "attn_lastq_x_fwd": _work_lastq_x_fwd, "attn_lastq_x_bwd": _work_lastq_x_bwd, "item_loss_train": _work_item_loss_train,
+def _work_full_ce_fwd(h, w, labels, mask, live, sums, train=True):
+    """Executed work over the live rows: the logits product (and the P.W product of the training form) per W chunk; W re-read
+    once per workgroup that has list entries (8 * TW live 16-row tiles each, TW = 2 at d <= 128: the others return at once), the
+    live rows of h read once, dh written in full (padded tiles as zeros) by the training form."""
+    n, d = h.shape
+    C = w.shape[0]
+    nl = float(mask.sum())
+    wgs = -(-int(live[0]) // (8 * (2 if d <= 128 else 1)))
+    return ("full_ce_fwd_kernel<%s,%s>" % (_tn(h), "train" if train else "infer"), 2.0 * nl * C * d * (2 if train else 1),
+            wgs * C * d * _esize(w) + nl * d * _esize(h) + (n * d * _esize(h) if train else 0) + n * 16)
+
+
+def _work_full_ce_dw(h, w, labels, mask, live, lse, sums, gout, dw):
+    """Two products per (live row, class): the logits again and dW += g^T h; the live rows of h re-read once per workgroup of
+    8 * CW 16-row tiles of W (CW = 2 at d <= 128), dW read and written once."""
+    n, d = h.shape
+    C = w.shape[0]
+    nl = float(mask.sum())
+    rows_wg = 16 * 8 * (2 if d <= 128 else 1)
+    return ("full_ce_dw_kernel<%s>" % _tn(h), 4.0 * nl * C * d,
+            (C / rows_wg + 1) * nl * (d * _esize(h) + 16) + C * d * (_esize(w) + 8))
+
+
+_WORK = {"full_ce_fwd": _work_full_ce_fwd, "full_ce_dw": _work_full_ce_dw, "attn_out_bwd": _work_attn_out_bwd, "ln_bwd": _work_ln_bwd, "gemm_tn_layer": _work_gemm_tn_layer, "item_loss_scatter_binned": _work_item_loss_scatter, "attn_lastq_x_fwd": _work_lastq_x_fwd, "attn_lastq_x_bwd": _work_lastq_x_bwd, "item_loss_train": _work_item_loss_train,
          "ffn_bwd_data": _work_ffn_bwd, "attn_fwd_x": _work_attn_fwd_x, "post_attn_fwd": _work_post_attn, "gemm_nt": _work_gemm_nt, "gemm_tn": _work_gemm_tn, "attn_fwd": _work_attn_fwd, "attn_bwd": _work_attn_bwd,
          "embed_pe_fwd": _work_embed_fwd, "item_loss_fwd": _work_item_loss, "item_loss_bwd": _work_item_loss}
 _PLAIN = ["dropout_", "cross_rows", "adam_multi", "adam_multi_dev", "disc_rows", "item_loss_bwd_binned", "embed_scatter_bwd", "bcast_add_ln", "seq_sum", "colsum", "outer_posmask", "interpolate",

@@ -52,6 +52,41 @@ class SampledLogits(object):
         return ops.bpr_loss(self.h, self.table, self.pos, self.neg, mask, self.k, self.skip_row, sas=sas)
 
 
+class FullLogits(object):
+    """Deferred logits over the whole catalogue (decoder_neg=False, the reference's `else:` branch): h @ weight.T with weight the
+    item table (AutoEnc4Rec.py:228-230: [B, L, V+1]) or projection_{a|b}.weight (AutoEnc4Rec_cross.py:216-220: [B, L, V_{a|b}]).
+    Holds the decoder states and the labels (dec_outputs)."""
+
+    def __init__(self, h, weight, labels):
+        self.h, self.weight, self.labels = h, weight, labels
+
+    def loss(self, mask):
+        """SampledCrossEntropyLoss over all classes with the 1-D label dec_outputs and masked mean (train_auto.py:44-51,
+        tools/utils.py:77-84 with neg_sample=False; quirk Q15) -- the fused kernels of csrc/full_ce.hip, no logits stored."""
+        return ops.full_softmax_loss(self.h, self.weight, self.labels, mask)
+
+    def dense(self):
+        """The [B, L, C] f32 logits tensor the reference's forward returns, forward only (no autograd graph): one HIP GEMM
+        (C x B x L x 4 bytes -- for inspection at small shapes; loss() never materialises it)."""
+        from . import hip
+        d = self.h.shape[-1]
+        h2 = self.h.detach().contiguous().view(-1, d)
+        out = hip.gemm_nt(h2, ops.shadow(self.weight), out_f32=True)
+        return out.view(tuple(self.h.shape[:-1]) + (self.weight.shape[0],))
+
+
+def check_recon_handle(logits, neg_sample):
+    """loss_ae's guard (training.py, auto_training.py): neg_sample must match the handle the model returned -- the reference dies
+    on a view over mismatched logits."""
+    if not neg_sample and not isinstance(logits, FullLogits):
+        raise ValueError("loss_ae(neg_sample=False) needs full-vocabulary logits, but the model returned sampled ones "
+                         "(param.decoder_neg=True and n_negs < vocab_size): set param.decoder_neg=False")
+    if neg_sample and isinstance(logits, FullLogits):
+        raise ValueError("loss_ae(neg_sample=True) needs sampled logits, but the model returned full-vocabulary ones "
+                         "(param.decoder_neg=False or n_negs >= vocab_size)")
+    return logits
+
+
 class Discriminator(nn.Module):
     """tools/utils.py:30-57: Linear-ReLU-Drop(.2) x3 + Linear; keys main.0/3/6/9.{weight,bias}."""
 
@@ -111,8 +146,9 @@ class MyAuto4Rec_c(nn.Module):
             self.decoder_a = stack(blocks.DecoderM)
             self.decoder_b = stack(blocks.DecoderM)
         if not param.decoder_neg:
-            raise NotImplementedError("full-vocabulary projection (decoder_neg=False) is outside the hot path "
-                                      "(train_gan.py:38 default is True)")
+            # full-catalogue output layer (AutoEnc4Rec_cross.py:76-78), between the decoders and the recommenders as there
+            self.projection_a = nn.Linear(param.d_model, param.vocab_size_a, bias=False)
+            self.projection_b = nn.Linear(param.d_model, param.vocab_size_b, bias=False)
         if not dec_rec:
             self.recommend_a = stack(blocks.DecoderM)
             self.recommend_b = stack(blocks.DecoderM)
@@ -170,11 +206,16 @@ class MyAuto4Rec_c(nn.Module):
         return self.src_emb_a.weight if domain == "a" else self.src_emb_b.weight
 
     def forward(self, enc_inputs, dec_inputs, dec_outputs, n_items, domain, mask):
-        """AutoEnc4Rec_cross.py:185-221 (decoder_neg branch) -> SampledLogits handle."""
+        """AutoEnc4Rec_cross.py:185-221 -> SampledLogits handle (decoder_neg branch) or FullLogits over projection_{a|b}
+        (the `else:` branch: V_{a|b} classes)."""
         dec_out, _, _ = self.get_dec_out(enc_inputs, dec_inputs, domain, mask)
         vocab = self.param.vocab_size_a if domain == "a" else self.param.vocab_size_b
         if not (self.param.decoder_neg and self.param.n_negs < vocab):
-            raise NotImplementedError("full-vocabulary logits are outside the hot path")
+            proj = getattr(self, "projection_a" if domain == "a" else "projection_b", None)
+            if proj is None:
+                raise ValueError("full-vocabulary logits need projection_%s: construct MyAuto4Rec_c with param.decoder_neg=False "
+                                 "(n_negs=%d >= vocab_size_%s=%d)" % (domain, self.param.n_negs, domain, vocab))
+            return FullLogits(dec_out, proj.weight, dec_outputs)
         return SampledLogits(dec_out, self.item_table(domain), dec_outputs, n_items, self.param.n_negs)
 
 
@@ -225,10 +266,11 @@ class MyAuto4Rec(nn.Module):
         return self.decode_with(self.decoder, enc_inputs, dec_inputs), None, None
 
     def forward(self, enc_inputs, dec_inputs, dec_outputs, n_items):
-        """AutoEnc4Rec.py:206-227 (sampled branch) -> SampledLogits handle."""
+        """AutoEnc4Rec.py:206-230 -> SampledLogits handle (sampled branch) or FullLogits over all V+1 rows of src_emb
+        (the `else:` branch)."""
         h, _, _ = self.get_dec_out(enc_inputs, dec_inputs)
         if not (self.param.decoder_neg and self.param.n_negs < self.param.vocab_size):
-            raise NotImplementedError("full-vocabulary logits are outside the hot path")
+            return FullLogits(h, self.src_emb.weight, dec_outputs)
         return SampledLogits(h, self.src_emb.weight, dec_outputs, n_items, self.param.n_negs, self.pad_index)
 
 

@@ -1230,6 +1230,55 @@ def bpr_loss(h, table, pos, neg, mask, k, skip_row=-1, sas=False):
 
 
 # ------------------------------------------------------------------------------------------------
+# full-catalogue softmax loss (decoder_neg=False, neg_sample=False): csrc/full_ce.hip
+# ------------------------------------------------------------------------------------------------
+class FullSoftmaxLoss(_Fn):
+    """sum_t m_t CE(h_t @ weight.T, label_t) / sum_t m_t (quirk Q15) without the [n, C] logits: the training-form forward leaves lse
+    and dh for an upstream gradient of 1; the backward scales dh and runs the vocab-major weight-gradient kernel into _gt(weight)
+    (every row of weight, a padding row included -- the matrix product's gradient reaches it in the reference's autograd)."""
+
+    @staticmethod
+    def forward(ctx, h, weight, labels, mask):
+        d = h.shape[-1]
+        h2 = h.contiguous().view(-1, d)
+        n = h2.shape[0]
+        labels = labels.contiguous().view(-1)
+        mask = mask.reshape(-1).contiguous()
+        if not hip.full_ce_supported(d, h2):
+            raise RuntimeError("full softmax loss: no kernel for d_model=%d in the %s tier (csrc/full_ce.hip: d in 64, 128, 256)"
+                               % (d, compute_tier()))
+        sums = torch.zeros(2, device=h2.device, dtype=torch.float32)
+        hip.sum_into(mask, sums[1:2])
+        if _DP is not None and _DP.world > 1:
+            _DP.global_count(sums[1:2])          # Q12: sum(l*m) / GLOBAL sum(m); grads are SUM-reduced
+        live = hip.live_tiles(mask, n)
+        train = _needs_grad(ctx)
+        lse, dh1 = hip.full_ce_fwd(h2, shadow(weight), labels, mask, live, sums, train=train)
+        ctx.weight = weight
+        ctx.shape = h.shape
+        ctx.consumed = not train
+        ctx.save_for_backward(h2, labels, mask, live, lse, sums, dh1)
+        return sums[0] / sums[1]
+
+    @staticmethod
+    def backward(ctx, gout):
+        h2, labels, mask, live, lse, sums, dh1 = ctx.saved_tensors
+        dW, ret = _gt(ctx.weight)
+        g1 = gout.reshape(1).to(torch.float32).contiguous()
+        w = shadow(ctx.weight)
+        if ctx.consumed:
+            # a second backward through a retained graph (or a forward without grad mode): the training form again, from scratch
+            lse, dh1 = hip.full_ce_fwd(h2, w, labels, mask, live, sums.clone(), train=True)
+        ctx.consumed = True                      # dh1 is scaled in place: it serves ONE backward
+        hip.full_ce_dw(h2, w, labels, mask, live, lse, sums, g1, dW)
+        return hip.scale_dev(dh1, g1).view(ctx.shape), ret, None, None
+
+
+def full_softmax_loss(h, weight, labels, mask):
+    return FullSoftmaxLoss.run(h, weight, labels, mask)
+
+
+# ------------------------------------------------------------------------------------------------
 # K12: MSE between the embeddings of overlapped users (gan_training.py:28-35, :494-507)
 # ------------------------------------------------------------------------------------------------
 class MseLossFn(_Fn):

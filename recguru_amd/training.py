@@ -18,6 +18,7 @@ import sys
 import torch
 
 from . import ops, profiling
+from .models import check_recon_handle
 from .optim import Adam
 
 LAMBDA = .1         # gan_training.py:21
@@ -99,10 +100,11 @@ def _unwrap(model):
 
 
 def loss_ae(model, enc_in, dec_in, dec_out, n_items, neg_sample, bs, sl, param, mask, device, domain="a"):
-    """Reconstruction loss: masked sampled-softmax CE with label 0 (tools/utils.py:60-87)."""
-    if not neg_sample:
-        raise NotImplementedError("full-vocabulary softmax (neg_sample=False) is outside the hot path")
-    return _unwrap(model)(enc_in, dec_in, dec_out, n_items, domain, mask).loss(mask)
+    """Reconstruction loss (tools/utils.py:60-87): masked sampled-softmax CE with label 0, or (neg_sample=False) the masked
+    softmax CE over domain's whole catalogue with label dec_out (quirk Q15)."""
+    logits = _unwrap(model)(enc_in, dec_in, dec_out, n_items, domain, mask)
+    return check_recon_handle(logits, neg_sample).loss(mask)
+
 
 
 def loss_bpr_func(model_train, enc_in, dec_in, dec_out, n_items, mask, domain, param):
