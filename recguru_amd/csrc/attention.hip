@@ -143,7 +143,8 @@ struct QLive {
 
 // One (b, h) head's dropout bits, p == 0.5 mode: word w of query row q covers keys 32w..32w+31 and equals
 // rg_hash(seed, idx >> 5) for idx = ((b*H + h)*L + q) * LPAD + key -- exactly what rg_keep() would hash,
-// computed once per head instead of once per lane and element.  Layout [word][query].
+// computed once per head instead of once per lane and element.  Layout [word][query].  idx is a 32-bit index, so its word is
+// the true word index mod 2^27 (the mask is applied past the 2^32 wrap exactly as rg_keep() applies it).
 // row0 (a multiple of 16): query rows in front of it belong to 16-row tiles of padded positions only (the forward skips those
 // tiles, the backward's dctx rows there are zeros by contract) -- their words are never looked at and are not hashed: 44 % of the
 // rows at the bench's lengths.  A group of 32 lanes takes 32 consecutive rows of one word index (consecutive LDS banks); the
@@ -159,7 +160,7 @@ __device__ __forceinline__ void fill_dmask(unsigned int* __restrict__ dmask, con
   while (blk < nblk) {
     const int row = row0 + 32 * blk + (tid & 31);
     if (row < LPK)
-      dmask[w * LPK + row] = (row < L && (unsigned int)w < nw) ? rg_hash(drop.seed, wbase + __umul24((unsigned int)row, nw) + w) : 0u;
+      dmask[w * LPK + row] = (row < L && (unsigned int)w < nw) ? rg_hash(drop.seed, (wbase + __umul24((unsigned int)row, nw) + w) & 0x07FFFFFFu) : 0u;
     w += DW;
     blk += DB;
     if (w >= NW) { w -= NW; ++blk; }

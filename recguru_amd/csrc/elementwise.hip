@@ -885,7 +885,7 @@ __global__ __launch_bounds__(EW_BLOCK) void cross_drop_scale_kernel(const int64_
     float acc = 0.f;
     if (drop.onebit) {
       int cnt = 0;
-      for (unsigned int w = 0; w < nw; ++w) cnt += __popc(rg_hash(drop.seed, row * nw + w) & live[w]);
+      for (unsigned int w = 0; w < nw; ++w) cnt += __popc(rg_hash(drop.seed, (row * nw + w) & 0x07FFFFFFu) & live[w]);   // word of the 32-bit idx
       acc = (float)cnt * drop.inv_keep;
     } else {
       for (int j = 0; j < L; ++j)

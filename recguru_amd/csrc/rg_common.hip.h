@@ -405,6 +405,9 @@ struct DropCfg {
 //   * otherwise: by the (idx & 1)-th 16-bit half of hash(idx >> 1) compared with p * 65536.
 // The group helpers (rg_keep4 / rg_keep8 / rg_keep4_pair) return the same decisions as rg_keep()
 // element by element; they only share the hash words.
+// idx is computed in 32 bits and wraps: masks repeat once a site's index passes 2^32.  A form that computes a hash word
+// directly (not through idx >> 5) must take the word of the 32-bit idx, i.e. word & 0x07FFFFFF (tests/dropmask.py restates
+// this contract on the host).
 __device__ __forceinline__ unsigned int rg_hash(unsigned int seed, unsigned int x) {
   x ^= seed;
   x ^= x >> 16; x *= 0x21f0aaadu;

@@ -125,8 +125,22 @@ def test_fused_critic_dropout_exact_vs_autograd_with_same_masks():
     Mw = [(ws["X2"][:2 * B] != 0).float() * keep, (ws["X3"][:2 * B] != 0).float() * keep, (ws["Y3"][:2 * B] != 0).float() * keep]
     # GP rows: u_i = (...) * m_i is non-zero exactly where the mask is (a product that is exactly 0.0 in f32 does not occur)
     Mg = [(ws["Y1"][2 * B:] != 0).float() * keep, (ws["Y2"][2 * B:] != 0).float() * keep, (ws["Y3"][2 * B:] != 0).float() * keep]
-    # about 20 % of the ReLU-active units of the first layer are dropped
+    # the same masks restated on the host (tests/dropmask.py): layer i of row r is element r * n_i + f under its own seed,
+    # W rows (real | fake, 2B) with seeds_w, GP rows (B) with seeds_g; the kernel's non-zeros lie inside the host's keeps, and
+    # the reference below runs on the host masks (ReLU zeroes the rest)
+    import dropmask as dm
+    ops.manual_seed(41)
+    sw, sg = [ops._draw() for _ in range(3)], [ops._draw() for _ in range(3)]
+    assert len(set(sw + sg)) == 6
+    Hw = [torch.from_numpy(dm.rowmajor_mask(s, p, 2 * B, n)).float().cuda() for s, n in zip(sw, (n1, n2, n3))]
+    Hg = [torch.from_numpy(dm.rowmajor_mask(s, p, B, n)).float().cuda() for s, n in zip(sg, (n1, n2, n3))]
+    for i in range(3):
+        assert bool(((Mw[i] != 0) <= (Hw[i] != 0)).all()) and bool(((Mg[i] != 0) <= (Hg[i] != 0)).all()), i
+    # about 20 % of the ReLU-active units of the first layer are dropped, exactly the host mask's drops
     h1 = torch.relu(torch.cat([real, fake]) @ m[0].weight.detach().T + m[0].bias.detach())
+    assert torch.equal((ws["X2"][:2 * B] == 0)[h1 > 1e-4], (Hw[0] == 0)[h1 > 1e-4])
+    Kw0 = Mw[0]
+    Mw, Mg = Hw, Hg
     act = h1 > 1e-6
     assert abs(float(((ws["X2"][:2 * B] == 0) & act).float().sum() / act.float().sum()) - p) < 0.03
 
@@ -151,7 +165,7 @@ def test_fused_critic_dropout_exact_vs_autograd_with_same_masks():
         torch.testing.assert_close(got[k], q.grad, rtol=2e-3, atol=2e-5 * s + 2e-7, msg=lambda m_: k + ": " + m_)
     # two calls draw different masks
     ops.critic_fused(D, real, fake, alpha)
-    assert not torch.equal(ws["X2"][:2 * B] != 0, Mw[0] != 0)
+    assert not torch.equal(ws["X2"][:2 * B] != 0, Kw0 != 0)
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])

@@ -854,6 +854,9 @@ def test_attn_dropout_consistency(dt, causal):
     live = A_ref > 1e-6
     frac = float((kept & live).float().sum() / live.float().sum())
     assert abs(frac - (1 - p)) < 0.06
+    import dropmask as dm          # the kept set is the host restatement's (index ((b*H + h)*L + q)*LPAD + key)
+    host = torch.from_numpy(dm.attn_mask(seed, p, H, L, range(B))[:, 0] != 0).cuda()
+    assert torch.equal(kept[live], host[live])
     t = dict(rtol=1e-5, atol=1e-6) if dt == torch.float32 else dict(rtol=2e-2, atol=2e-3)
     torch.testing.assert_close(A_drop[kept], (A_ref / (1 - p))[kept], **t)
     # backward vs autograd through the explicit dropped map
