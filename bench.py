@@ -15,11 +15,16 @@ seq_len=200 / hidden=128 / batch=4096 per GPU; per-GPU work is fixed as N grows 
          --master-port P bench.py --gpus N --steps K --warmup W
   python bench.py --mode ae                                 (the AE step alone: one train_recon_x iteration, 2*B sequences)
   python bench.py --dump-outputs DIR                        (also writes what the last timed step computed: DIR/<name>.npy)
+  python bench.py --full                                    (also everything beside the headline figure: see below)
 
-Prints ONE JSON line on rank 0.  The `roofline` object is measured live in this process with HIP
-events on the launch stream around every launch of the dominant kernel (an instrumented pass of the
-same step after the timed region); `cpu_baseline` times the CPU oracle (oracle/recguru_oracle.py,
-a port of the reference arithmetic) on a bounded sample of the same workload on the host cores.
+Prints ONE JSON line on rank 0.  A plain run does only what the headline figure needs: it sets up,
+runs the warm-up and the timed steps, writes --dump-outputs and prints the line.  Everything else
+the line can carry is measured with --full only, after the timed region: the `roofline` object
+(measured live in this process with HIP events on the launch stream around every launch of the
+dominant kernel, an instrumented pass of the same step), the full-length-users and AE-step figures,
+the bf16x3 / mixed / f32 tiers, the host's own cost per step, the config-5 shape, the gradient
+exchange at N > 1, and `cpu_baseline`, which times the CPU oracle (oracle/recguru_oracle.py, a port
+of the reference arithmetic) on a bounded sample of the same workload on the host cores.
 """
 import argparse
 import glob
@@ -136,9 +141,13 @@ def parse():
     ap.add_argument("--mode", choices=["gan", "ae"], default="gan",
                     help="gan: the AE+GAN step = one phase-2 iteration of train_gan_all (BASELINE.json's metric); "
                          "ae: the AE step = one train_recon_x iteration (SURVEY 8d (i))")
-    ap.add_argument("--ae_steps", type=int, default=8, help="gan mode: AE steps timed after the main region for the "
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline figure (the options whose help "
+                         "starts with --full tune those legs); a plain run only sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the line")
+    ap.add_argument("--ae_steps", type=int, default=8, help="--full, gan mode: AE steps timed after the main region for the "
                     "`ae_step` object of the line (0: skip)")
-    ap.add_argument("--full_length_steps", type=int, default=4, help="gan mode: steps timed with full-length users (no "
+    ap.add_argument("--full_length_steps", type=int, default=4, help="--full, gan mode: steps timed with full-length users (no "
                     "padding to skip) for `value_full_length` (0: skip)")
     ap.add_argument("--device_sampler", action="store_true",
                     help="loaders included: assemble every batch and draw fresh negatives on the GPU (recguru_amd.sampler) "
@@ -162,16 +171,17 @@ def parse():
     ap.add_argument("--dropout", type=float, default=0.5,
                     help="transformer dropout (reference config_auto4rec.py:225: 0.5); the discriminator's 0.2 is active too")
     ap.add_argument("--batches_per_domain", type=int, default=2, help="distinct synthetic batches cycled")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
-    ap.add_argument("--cpu_batch", type=int, default=64, help="users per domain per draw of the CPU-oracle sample (SURVEY 8d: 64..128)")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="--full: skip `cpu_baseline`")
+    ap.add_argument("--cpu_batch", type=int, default=64, help="--full: users per domain per draw of the CPU-oracle sample "
+                    "(SURVEY 8d: 64..128)")
     ap.add_argument("--min_len", type=int, default=5,
                     help="synthetic user lengths are U{min_len..L+20}; 5 (default) pads 44 %% of the positions, >= L-1 none")
-    ap.add_argument("--no_roofline", action="store_true")
-    ap.add_argument("--tier_steps", type=int, default=3, help="default (bf16) line only: steps timed in each of the two tiers that "
+    ap.add_argument("--no_roofline", action="store_true", help="--full: skip the instrumented passes of `roofline`")
+    ap.add_argument("--tier_steps", type=int, default=3, help="--full, default (bf16) line only: steps timed in each of the two tiers that "
                     "meet rtol 1e-3 / atol 1e-5 -- bf16x3 and f32 -- for the `tiers` object of the line (0: skip)")
-    ap.add_argument("--host_only_steps", type=int, default=5, help="default line only: steps of the same AE+GAN step at 32 users per draw "
+    ap.add_argument("--host_only_steps", type=int, default=5, help="--full, default line only: steps of the same AE+GAN step at 32 users per draw "
                     "(the host's own cost per step) for `config.host_only` (0: skip)")
-    ap.add_argument("--config5_steps", type=int, default=2, help="default line only: steps of BASELINE configs[4]'s single-GPU shape "
+    ap.add_argument("--config5_steps", type=int, default=2, help="--full, default line only: steps of BASELINE configs[4]'s single-GPU shape "
                     "(2 M items per domain, L=400, d=256, H=8, k=1024, B=4096) timed for the `config5` object (0: skip)")
     ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (its losses, the parameters it left "
@@ -524,8 +534,8 @@ CONFIG5 = dict(items=2000000, seq_len=400, d_model=256, n_head=8, n_negs=1024, b
 
 def config5_leg(args, device, rank, world, dp):
     """BASELINE configs[4]'s per-GPU shape (large-catalogue stress: 2 M items per domain, seq_len 400, hidden 256, sampled
-    softmax k = 1024, batch 4096) through the same step, a few timed steps + its own roofline pass, so that the driver's run
-    of the default line times it.  Skipped with a stated reason when the GPU has < 80 GB free."""
+    softmax k = 1024, batch 4096) through the same step, a few timed steps + its own roofline pass, so that the --full run
+    of the default shape times it.  Skipped with a stated reason when the GPU has < 80 GB free."""
     free = torch.cuda.mem_get_info()[0]
     if free < (80 << 30):
         return {"skipped": "%.0f GB of HBM free, 80 GB needed (2 x 13 GB of negative ids, two 2 M x 256 tables with gradients "
@@ -616,21 +626,22 @@ def main():
     if args.dump_outputs and rank == 0:        # before anything below runs the step again (the parameters are the last timed step's)
         dump_outputs(args.dump_outputs, names, out, G, None if ae else D)
 
-    # N > 1: what the gradient exchange of ONE step moved and what it cost the compute stream (every rank takes part)
+    # everything below the headline figure runs with --full only.  N > 1: what the gradient exchange of ONE step moved and
+    # what it cost the compute stream (every rank takes part)
     exchange = None
-    if dp:
+    if args.full and dp:
         dp.start_stats()
         step()
         exchange = dp.stop_stats()
         dp.barrier()
-    roof = None if args.no_roofline else roofline_pass(step, args.dtype, rank)
+    roof = roofline_pass(step, args.dtype, rank) if args.full and not args.no_roofline else None
     if dp:
         dp.barrier()
 
     # the same step with FULL-LENGTH users (no padded position anywhere: nothing for the live-tile lists to skip) and the
-    # AE step, a few steps each, so that the default line carries them
+    # AE step, a few steps each, so that the --full line carries them
     full = ae_line = None
-    if not ae and args.full_length_steps > 0 and args.min_len < args.seq_len - 1:
+    if args.full and not ae and args.full_length_steps > 0 and args.min_len < args.seq_len - 1:
         del step, loaders
         torch.cuda.empty_cache()
         loaders = make_loaders(args, device, rank, args.seq_len - 1)
@@ -641,7 +652,7 @@ def main():
         del step, loaders
         torch.cuda.empty_cache()
         loaders = make_loaders(args, device, rank, args.min_len)       # back to the default length distribution
-    if not ae and args.ae_steps > 0:
+    if args.full and not ae and args.ae_steps > 0:
         step = make_ae_step(param, G, opt_rec, loaders, device, dp)
         dta, _, outa = timed(step, 3, args.ae_steps, dp, device)      # (3 untimed steps: the allocator regrows after the full-length leg)
         ae_line = {"metric": "user-sequences/sec (AE step)", "value": round(2 * args.batch * world * args.ae_steps / dta, 1),
@@ -651,9 +662,9 @@ def main():
                                "backward, Noam-Adam", "last_step": {"recon_a": float(outa[0]), "recon_b": float(outa[1])}}
 
     # The tiers that meet the north-star tolerance (rtol 1e-3 / atol 1e-5 against the fp32 reference, tests/test_steps_gpu.py):
-    # the same step, same model and batches, a few timed steps each -- so that the driver's run times them too
+    # the same step, same model and batches, a few timed steps each -- so that the --full line carries them too
     tiers = None
-    if not ae and args.dtype == "bf16" and args.residual == "bf16" and args.tier_steps > 0:
+    if args.full and not ae and args.dtype == "bf16" and args.residual == "bf16" and args.tier_steps > 0:
         tiers = {}
         for tier in ("bf16x3", "mixed", "f32"):
             ops.set_compute_dtype(tier)
@@ -683,7 +694,8 @@ def main():
     # what the HOST needs for a step when the GPU work is negligible (the same step at 32 users per draw): `host_enqueue_ms_per_step`
     # above is the time the host spent enqueueing INCLUDING the waits on a full launch queue, not what it needs
     host_only = None
-    if not ae and args.dtype == "bf16" and args.residual == "bf16" and args.batch >= 1024 and args.host_only_steps > 0 and not dp:
+    if args.full and not ae and args.dtype == "bf16" and args.residual == "bf16" and args.batch >= 1024 and args.host_only_steps > 0 \
+            and not dp:
         a_s = argparse.Namespace(**vars(args))
         a_s.batch, a_s.batches_per_domain = 32, 2
         ops.set_compute_dtype(args.dtype)
@@ -696,8 +708,8 @@ def main():
         del step_s, lds, Gs, Ds, ogs, ods, ors
 
     c5 = None
-    if not ae and args.dtype == "bf16" and args.residual == "bf16" and args.config5_steps > 0 and args.items == 100000 and args.seq_len == 200 \
-            and args.batch == 4096:
+    if args.full and not ae and args.dtype == "bf16" and args.residual == "bf16" and args.config5_steps > 0 and args.items == 100000 \
+            and args.seq_len == 200 and args.batch == 4096:
         del loaders, G, D, opt_g, opt_d, opt_rec
         step = None
         torch.cuda.empty_cache()
@@ -705,7 +717,7 @@ def main():
         c5 = config5_leg(args, device, rank, world, dp)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     if rank == 0:
@@ -729,9 +741,9 @@ def main():
                        "parallelism": "dp%d" % world, "host_enqueue_ms_per_step": round(t_host / args.steps * 1e3, 2),
                        "host_only": host_only,
                        "last_step": dict(zip(names, losses))},
-            "roofline": roof, "cpu_baseline": cpu,
+            "roofline": roof, "cpu_baseline": cpu, "full": args.full,
         }
-        if dp:
+        if exchange:
             # what the collective layer itself saw (a SCALE record can then show that RCCL ran N ranks on N devices)
             line["exchange"] = {"backend": exchange["backend"], "collective_world": exchange["world"],
                                 "visible_devices": torch.cuda.device_count(), "device_of_rank0": device,
@@ -748,7 +760,7 @@ def main():
             line["peaks_on_box"] = {"file": PEAKS_FILE, **{k: PEAKS[k] for k in ("hbm_read_best", "hbm_write_best", "hbm_copy_best", "hbm_triad_best",
                                                                                  "hbm_read_only", "hbm_write_only", "hbm_copy_kernel", "hbm_triad",
                                                                                 "gather_copy_512B_rows_u4", "mfma_16x16x32_bf16_4wave_per_simd")
-                                                           if k in PEAKS}} if PEAKS else None
+                                                           if k in PEAKS}} if PEAKS and args.full else None
             line["config5"] = c5
         os.write(line_fd, (json.dumps(line) + "\n").encode())
     if dp:

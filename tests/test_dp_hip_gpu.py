@@ -294,7 +294,7 @@ def test_bench_self_launch_two_ranks():
     prints one JSON line with n_gpus = 2 and exits 0.  On a 1-GPU box both ranks share GPU 0 over gloo (the debug knobs);
     with two GPUs the same command runs over RCCL."""
     env = {} if _two_gpus() else {"RG_BENCH_SINGLE_DEVICE": "1", "RG_BENCH_BACKEND": "gloo"}
-    line = _bench(["--gpus", "2"] + SMALL, env)
+    line = _bench(["--gpus", "2", "--full"] + SMALL, env)
     assert line["n_gpus"] == 2 and line["config"]["parallelism"] == "dp2" and line["value"] > 0
     assert line["config"]["sequences_per_step"] == 12 * 64 * 2
     assert line["ae_step"]["sequences_per_step"] == 2 * 64 * 2 and line["value_full_length"] > 0
@@ -318,7 +318,7 @@ def test_bench_self_launch_four_ranks():
     handed to all-reduce."""
     n = MAX_GPU_RANKS
     env = {} if _gpus() >= n else {"RG_BENCH_SINGLE_DEVICE": "1", "RG_BENCH_BACKEND": "gloo"}
-    line = _bench(["--gpus", str(n), "--batch", "64", "--items", "100000", "--steps", "2", "--warmup", "1", "--no_cpu_baseline",
+    line = _bench(["--gpus", str(n), "--full", "--batch", "64", "--items", "100000", "--steps", "2", "--warmup", "1", "--no_cpu_baseline",
                    "--batches_per_domain", "1", "--tier_steps", "0", "--ae_steps", "0", "--full_length_steps", "0", "--host_only_steps", "0"],
                   env, timeout=2400)
     assert line["n_gpus"] == n and line["config"]["parallelism"] == "dp%d" % n and line["value"] > 0
@@ -337,7 +337,7 @@ def test_bench_line_through_rccl_group_of_one():
     line gains `exchange` with backend nccl; and stdout still carries exactly one line -- librccl's version banner, printed through
     C stdio when the communicator is created, used to land behind the JSON line at exit."""
     try:
-        line = _bench(["--gpus", "1", "--tier_steps", "0"] + SMALL, {"RG_DP_FORCE": "1"})
+        line = _bench(["--gpus", "1", "--full", "--tier_steps", "0"] + SMALL, {"RG_DP_FORCE": "1"})
     except AssertionError as e:
         if _rccl_unavailable(str(e)):
             pytest.skip("RCCL cannot initialise on this box: %s" % str(e)[-300:])
@@ -348,15 +348,32 @@ def test_bench_line_through_rccl_group_of_one():
 
 
 def test_bench_line_contract_single_gpu():
-    """The default line: BASELINE.json's metric, roofline (frac = executed rows, frac_nominal beside it), the AE-step
+    """The --full line: BASELINE.json's metric, roofline (frac = executed rows, frac_nominal beside it), the AE-step
     object and the full-length-users value; --mode ae reports the AE step as the metric."""
-    line = _bench(["--gpus", "1"] + SMALL)
+    line = _bench(["--gpus", "1", "--full"] + SMALL)
     assert line["metric"] == "user-sequences/sec (AE+GAN step)" and line["n_gpus"] == 1
     r = line["roofline"]
     assert r["bound"] in ("hbm", "mfma") and 0 < r["frac"] <= r["frac_nominal"] + 1e-9
     assert line["ae_step"]["value"] > 0 and line["value_full_length"] > 0
     assert "exchange" not in line and line["config5"] is None          # (config-5 rides only in the default-shape line)
     assert line["value_bf16x3_tier"] == line["tiers"]["bf16x3"]["value"] > 0 and line["value_f32_tier"] > 0
-    ae = _bench(["--gpus", "1", "--mode", "ae"] + SMALL)
+    ae = _bench(["--gpus", "1", "--full", "--mode", "ae"] + SMALL)
     assert ae["metric"] == "user-sequences/sec (AE step)" and ae["config"]["sequences_per_step"] == 2 * 64
     assert "ae_step" not in ae and ae["value"] > 0
+
+
+def test_bench_plain_line_single_gpu(tmp_path):
+    """A plain run (no --full) times the headline figure and nothing else: the same metric, no leg of the --full line, no CPU
+    baseline even when it is not switched off; --dump-outputs still writes what the last timed step computed."""
+    args = [a for a in SMALL if a != "--no_cpu_baseline"]
+    line = _bench(["--gpus", "1", "--dump-outputs", str(tmp_path)] + args)
+    assert line["metric"] == "user-sequences/sec (AE+GAN step)" and line["unit"] == "user-sequences/sec"
+    assert line["higher_is_better"] is True and line["dtype"] == "bf16" and line["full"] is False
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 2 and line["warmup"] == 1
+    assert line["value"] == pytest.approx(12 * 64 * 1e3 / line["ms_per_step"], rel=1e-3)
+    for k in ("roofline", "cpu_baseline", "ae_step", "tiers", "value_full_length", "config5", "peaks_on_box"):
+        assert line[k] is None, k
+    assert line["config"]["host_only"] is None and "exchange" not in line
+    for name, v in line["config"]["last_step"].items():
+        assert np.isfinite(v) and float(np.load(os.path.join(str(tmp_path), name + ".npy"))) == v, name
+    assert os.path.exists(os.path.join(str(tmp_path), "G.src_emb_a.weight.npy"))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-4 A/B lines quoted in DESIGN 6 / 6a, one GPU-box call:  bash tools/ab_round4.sh  (writes gpurun_out/ab4/*.json and a summary)
 mkdir -p gpurun_out/ab4
-Q="--no_cpu_baseline --ae_steps 0 --full_length_steps 0 --tier_steps 0 --config5_steps 0"
+Q="--full --no_cpu_baseline --ae_steps 0 --full_length_steps 0 --tier_steps 0 --config5_steps 0"
 run() { name=$1; shift; env "$@" python bench.py $BARGS $Q > gpurun_out/ab4/$name.json 2>> gpurun_out/ab4/err.log; }
 BARGS="--steps 10 --warmup 3"
 run bf16_default RG_NOOP=1

@@ -6,7 +6,7 @@ set -u
 cd "$(dirname "$0")/.."
 stage=${1:-nopk}
 O=gpurun_out/r06/$stage; mkdir -p $O
-QUICK="--no_cpu_baseline --tier_steps 0 --host_only_steps 0 --config5_steps 0 --ae_steps 0 --full_length_steps 0 --steps 20 --warmup 5"
+QUICK="--full --no_cpu_baseline --tier_steps 0 --host_only_steps 0 --config5_steps 0 --ae_steps 0 --full_length_steps 0 --steps 20 --warmup 5"
 ab_bench() {   # name lib [extra bench flags]
   local name=$1 libp=$2; shift 2
   if [ -n "$libp" ]; then RG_HIP_LIB=$libp python bench.py $QUICK "$@" > $O/bench_$name.json 2> $O/bench_$name.err

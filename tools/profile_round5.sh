@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_$RD
 rm -rf $O && mkdir -p $O
-NB="--no_cpu_baseline --ae_steps 0 --full_length_steps 0 --tier_steps 0 --config5_steps 0 --host_only_steps 0"
+NB="--full --no_cpu_baseline --ae_steps 0 --full_length_steps 0 --tier_steps 0 --config5_steps 0 --host_only_steps 0"
 python3 $R/tools/peaks.py $O/peaks.txt > /dev/null 2>&1
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --steps 4 --warmup 1 $NB > $O/bench_under_rocprof.json 2> $O/kt.err
 find $O/kt -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats.csv
@@ -37,17 +37,17 @@ rm -rf gpurun_out/pmc_attn
 bash tools/pmc_attn.sh 0.5 x3 > $O/sq_attention_bf16x3.txt 2>&1
 rm -rf gpurun_out/pmc_attn
 # ---- the plain lines
-timeout 900 python3 bench.py 2> $O/bench.err | tail -1 > $O/bench.json
-timeout 300 python3 bench.py --dropout 0 --no_cpu_baseline --tier_steps 0 --config5_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_dropout0.json
-timeout 300 python3 bench.py --device_sampler --no_cpu_baseline --tier_steps 0 --config5_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_device_sampler.json
-timeout 300 python3 bench.py --mode ae --no_cpu_baseline --tier_steps 0 --config5_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_ae_step.json
-timeout 600 python3 bench.py --dtype bf16x3 --steps 5 --warmup 2 --no_cpu_baseline --ae_steps 0 --full_length_steps 0 2>> $O/bench.err | tail -1 > $O/bench_bf16x3_tier.json
+timeout 900 python3 bench.py --full 2> $O/bench.err | tail -1 > $O/bench.json
+timeout 300 python3 bench.py --full --dropout 0 --no_cpu_baseline --tier_steps 0 --config5_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_dropout0.json
+timeout 300 python3 bench.py --full --device_sampler --no_cpu_baseline --tier_steps 0 --config5_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_device_sampler.json
+timeout 300 python3 bench.py --full --mode ae --no_cpu_baseline --tier_steps 0 --config5_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_ae_step.json
+timeout 600 python3 bench.py --full --dtype bf16x3 --steps 5 --warmup 2 --no_cpu_baseline --ae_steps 0 --full_length_steps 0 2>> $O/bench.err | tail -1 > $O/bench_bf16x3_tier.json
 timeout 300 python3 tools/hostprof.py > $O/hostprof.txt 2>&1
 timeout 300 python3 tools/hostprof2.py > $O/hostprof_torch_kernels.txt 2>&1
 timeout 300 python3 tools/kb_embed_c5.py > $O/kb_embed_config5_table.txt 2>&1
 RG_EMBED_ROWS=1 timeout 300 python3 tools/kb_embed_c5.py > $O/kb_embed_config5_table_row_form_kernel.txt 2>&1
 # ---- config-5 (2 M items, L = 400, d = 256, k = 1024) at B = 4096: with the fused d_model = 256 forward block and without
-C5="--items 2000000 --seq_len 400 --d_model 256 --n_head 8 --n_negs 1024 --batch 4096 --batches_per_domain 1 --ae_steps 0 --full_length_steps 0 --tier_steps 0 --config5_steps 0 --host_only_steps 0 --no_cpu_baseline"
+C5="--full --items 2000000 --seq_len 400 --d_model 256 --n_head 8 --n_negs 1024 --batch 4096 --batches_per_domain 1 --ae_steps 0 --full_length_steps 0 --tier_steps 0 --config5_steps 0 --host_only_steps 0 --no_cpu_baseline"
 mkdir -p $O/c5
 timeout 900 python3 bench.py $C5 --steps 3 --warmup 1 2> $O/c5/bench.err | tail -1 > $O/c5/bench.json
 RG_NO_PA256=1 timeout 900 python3 bench.py $C5 --steps 3 --warmup 1 2>> $O/c5/bench.err | tail -1 > $O/c5/bench_unfused_block.json

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_$RD
 rm -rf $O && mkdir -p $O
-NB="--no_cpu_baseline --ae_steps 0 --full_length_steps 0 --tier_steps 0 --config5_steps 0 --host_only_steps 0"
+NB="--full --no_cpu_baseline --ae_steps 0 --full_length_steps 0 --tier_steps 0 --config5_steps 0 --host_only_steps 0"
 python3 $R/tools/peaks.py $O/peaks.txt > /dev/null 2>&1
 mkdir -p $R/profiles/$RD && cp $O/peaks.txt $O/peaks.json $R/profiles/$RD/      # bench.py reads the newest profiles/rNN/peaks.json: THIS box's
 (cd $R && tools/embed_ladder_probe > $O/embed_ladder.txt 2>&1; tools/ffn_shape_probe_bin > $O/ffn_shape_probe_32x32x16.txt 2>&1)
@@ -40,11 +40,11 @@ rm -rf gpurun_out/pmc_attn
 bash tools/pmc_attn.sh 0.5 x3 > $O/sq_attention_bf16x3.txt 2>&1
 rm -rf gpurun_out/pmc_attn
 # ---- the plain lines
-timeout 900 python3 bench.py 2> $O/bench.err | tail -1 > $O/bench.json
-timeout 300 python3 bench.py --dropout 0 --no_cpu_baseline --tier_steps 0 --config5_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_dropout0.json
-timeout 300 python3 bench.py --device_sampler --no_cpu_baseline --tier_steps 0 --config5_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_device_sampler.json
-timeout 300 python3 bench.py --mode ae --no_cpu_baseline --tier_steps 0 --config5_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_ae_step.json
-timeout 600 python3 bench.py --dtype bf16x3 --steps 5 --warmup 2 --no_cpu_baseline --ae_steps 0 --full_length_steps 0 2>> $O/bench.err | tail -1 > $O/bench_bf16x3_tier.json
+timeout 900 python3 bench.py --full 2> $O/bench.err | tail -1 > $O/bench.json
+timeout 300 python3 bench.py --full --dropout 0 --no_cpu_baseline --tier_steps 0 --config5_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_dropout0.json
+timeout 300 python3 bench.py --full --device_sampler --no_cpu_baseline --tier_steps 0 --config5_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_device_sampler.json
+timeout 300 python3 bench.py --full --mode ae --no_cpu_baseline --tier_steps 0 --config5_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_ae_step.json
+timeout 600 python3 bench.py --full --dtype bf16x3 --steps 5 --warmup 2 --no_cpu_baseline --ae_steps 0 --full_length_steps 0 2>> $O/bench.err | tail -1 > $O/bench_bf16x3_tier.json
 timeout 300 python3 tools/hostprof.py > $O/hostprof.txt 2>&1
 timeout 300 python3 tools/hostprof2.py > $O/hostprof_torch_kernels.txt 2>&1
 timeout 300 python3 tools/kb_embed_c5.py > $O/kb_embed_config5_table.txt 2>&1
@@ -55,11 +55,11 @@ for t in bf16 bf16x3; do timeout 300 python3 tools/kb_post_attn.py $t > $O/kb_po
 timeout 300 python3 tools/kb_attn_hm.py > $O/kb_attn_hm.txt 2>&1
 # the self-launched multi-rank bench line in the form a 1-GPU box can hold: four rank processes on GPU 0 over gloo (at most 6 processes may
 # hold the GPU at once; profiles/r06/bench_dp8_gloo_on_one_gpu.json was recorded with eight, before that limit)
-RG_BENCH_SINGLE_DEVICE=1 RG_BENCH_BACKEND=gloo timeout 1200 python3 bench.py --gpus 4 --batch 64 --steps 2 --warmup 1 --no_cpu_baseline --batches_per_domain 1 --tier_steps 0 --ae_steps 0 --full_length_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_dp4_gloo_on_one_gpu.json
+RG_BENCH_SINGLE_DEVICE=1 RG_BENCH_BACKEND=gloo timeout 1200 python3 bench.py --full --gpus 4 --batch 64 --steps 2 --warmup 1 --no_cpu_baseline --batches_per_domain 1 --tier_steps 0 --ae_steps 0 --full_length_steps 0 --host_only_steps 0 2>> $O/bench.err | tail -1 > $O/bench_dp4_gloo_on_one_gpu.json
 # the entry script's own per-kernel tables
 rm -rf /tmp/rg_prof_res && timeout 900 python3 train_gan.py --cross True --synthetic 8192 --seq_len 200 --d_model 128 --n_head 4 --batch_size 4096 --batch_size_val 256 --vocab_size_a 100000 --vocab_size_b 100000 --n_negs 30 --phase1_steps 5 --steps_tune 10 --result_path /tmp/rg_prof_res --profile $O/train_gan_profile --profile_steps 3 > $O/train_gan_profile.log 2>&1
 # ---- config-5 (2 M items, L = 400, d = 256, k = 1024) at B = 4096: with the fused d_model = 256 forward block and without
-C5="--items 2000000 --seq_len 400 --d_model 256 --n_head 8 --n_negs 1024 --batch 4096 --batches_per_domain 1 --ae_steps 0 --full_length_steps 0 --tier_steps 0 --config5_steps 0 --host_only_steps 0 --no_cpu_baseline"
+C5="--full --items 2000000 --seq_len 400 --d_model 256 --n_head 8 --n_negs 1024 --batch 4096 --batches_per_domain 1 --ae_steps 0 --full_length_steps 0 --tier_steps 0 --config5_steps 0 --host_only_steps 0 --no_cpu_baseline"
 mkdir -p $O/c5
 timeout 900 python3 bench.py $C5 --steps 3 --warmup 1 2> $O/c5/bench.err | tail -1 > $O/c5/bench.json
 RG_NO_PA256=1 timeout 900 python3 bench.py $C5 --steps 3 --warmup 1 2>> $O/c5/bench.err | tail -1 > $O/c5/bench_unfused_block.json

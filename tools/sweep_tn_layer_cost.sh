@@ -2,7 +2,7 @@
 # Sweep of the per-slot cost factors of rg_gemm_tn_layer's workgroup split (hip.LAYER_COST, RG_TN_LAYER_COST), one GPU-box call:
 #   bash tools/sweep_tn_layer_cost.sh            -> profiles/r05/ab/tn_layer_cost_sweep.txt was written from its output
 O=gpurun_out/tn_layer_cost; mkdir -p $O
-NB="--no_cpu_baseline --ae_steps 0 --full_length_steps 0 --tier_steps 0 --config5_steps 0 --host_only_steps 0"
+NB="--full --no_cpu_baseline --ae_steps 0 --full_length_steps 0 --tier_steps 0 --config5_steps 0 --host_only_steps 0"
 one() {   # file tag, extra bench args, kernel name
   python - "$1" "$3" <<'PY'
 import json, sys
