@@ -520,6 +520,36 @@ typedef struct {
 } rg_rank_args;
 int rg_rank_scores(const rg_rank_args* args /* host */, int dtype, void* stream);
 
+/* ---- full-catalogue top-K and exact rank (csrc/topk.hip) -------------------------------------------------
+ * One pass over the item table that never forms [B, n_rows]: score(b, i) = h[b] . table[i], f32 accumulation, dtype RG_BF16
+ * (bf16 operands) or RG_X3 (f32 buffers, split bf16 operands: the bf16x3 and the f32 tier).  d in {64, 128, 256}, 0 <= K <= 128
+ * (0 = rank only), n_rows < 2^31; anything else is RG_ERR_UNSUPPORTED.
+ *   rank[b]       number of catalogue ids i != target[b], not in row b's exclusion list, with score(b, i) > score(b, target[b])
+ *                 (strictly, as in the candidate-list ranking above); the target itself is never excluded.  The targets are checked
+ *                 against the catalogue range on the host before anything is launched: a call that asks for ranks copies target
+ *                 back and waits for the stream once.
+ *   topk_ids[b]   the K non-excluded catalogue ids with the highest scores, score descending, ties by ascending id; topk_scores
+ *                 their scores; fewer than K eligible ids: trailing slots hold id -1 and score -inf.
+ * A score is a function of (h[b], table[i]) alone -- not of B, the workgroup or the position in a tile -- so results are bit-identical
+ * across repeats and across batch splits; no float atomics (the same code in the deterministic library).
+ * Workspace: align256(4 B) + S B K 8 bytes with S = clamp(ceil(1024 / ceil(B / 64)), 1, 64) catalogue slices; it does not grow with
+ * n_rows.  The workspace query returns 0 for an unsupported shape. */
+typedef struct {
+  const void* h;                 /* [B, d]   operand dtype */
+  const void* table;             /* [rows, d] operand dtype */
+  long long first_row, n_rows;   /* the catalogue is rows first_row .. first_row + n_rows - 1 of table */
+  const int64_t* target;         /* [B] or NULL; each inside the catalogue range */
+  const int64_t* excl;           /* CSR values: sorted, unique ids per batch row, or NULL */
+  const int64_t* excl_off;       /* [B + 1] offsets into excl, or NULL */
+  int64_t* topk_ids;             /* [B, K] out, or NULL when K == 0 */
+  float* topk_scores;            /* [B, K] out, or NULL */
+  int* rank;                     /* [B] out, or NULL (requires target) */
+  void* workspace; size_t workspace_bytes;
+  int B, d, K;
+} rg_topk_args;
+size_t rg_topk_workspace(int B, int d, long long n_rows, int K);  /* 0 = unsupported shape */
+int rg_topk_scores(const rg_topk_args* args /* host */, int dtype, void* stream);
+
 /* ---- fused post-attention block, forward -------------------------------------------------------------
  * y = LN(ctx.Wo^T + bo + x) [; y = LN(y + o_bcast[b])] ; out = LN(gelu(y.W1^T + b1).W2^T + b2 + y) * rowmask
  * = MultiHeadAttention tail (Transformer/transformer.py:160-161) [+ collapsed dec_enc_attn, :259, Q1]

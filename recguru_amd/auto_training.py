@@ -17,7 +17,7 @@ import torch
 from . import ops, profiling
 from .models import check_recon_handle
 from .optim import Adam
-from .training import _extend_result, _new_result, plot
+from .training import _extend_result, _new_result, plot, seen_rows
 
 
 def _unwrap(model):
@@ -93,6 +93,49 @@ def evaluation(model_train, data_loader, de, param_config, k_val=None, sas=False
                 res[str(k)]["ndcg_" + tag].append(metrics.NDCG_at_k_batch(r, k))
                 res[str(k)]["mrr_" + tag].append(metrics.mrr_at_k_batch(r, k))
     return [result_freq, result_rand]
+
+
+def recommend(model, enc_in, dec_in, k, param, exclude_seen=True, sas=False):
+    """training.recommend for the single-domain model: the k catalogue items (ids 1 .. vocab_size - 1) that score highest against
+    the last recommender-decoder state, (ids [B, k] int64, scores [B, k] f32); with exclude_seen none of the user's own items."""
+    if sas:
+        raise NotImplementedError("SASRec scoring is outside the hot path")
+    from . import hip
+    m = _unwrap(model)
+    with torch.no_grad():
+        h = m.get_embedding(enc_in, dec_in)[:, -1, :].contiguous()
+    excl, off = seen_rows(enc_in, 0, param.vocab_size) if exclude_seen else (None, None)
+    ids, scores, _ = hip.topk_scores(h, ops.shadow(m.AutoEnc.src_emb.weight), k, 1, param.vocab_size - 1, excl=excl, excl_off=off)
+    return ids, scores
+
+
+def evaluation_full(model_train, data_loader, de, param_config, k_val=None, sas=False):
+    """evaluation() with unsampled metrics: the exact rank of every validation / test target among all catalogue items (the
+    full-catalogue kernel); the loader's sampled candidates are ignored.  Returns one result dict in evaluation()'s layout."""
+    from . import hip, metrics
+    if sas:
+        raise NotImplementedError("SASRec scoring is outside the hot path")
+    if k_val is None:
+        k_val = [5, 10, 20, 30]
+    model_train.eval()
+    m = _unwrap(model_train)
+    result = _new_result(k_val)[0]
+    ranks = {"eval": [], "test": []}
+    table = ops.shadow(m.AutoEnc.src_emb.weight)
+    for eval_data, test_data, _, _ in data_loader:
+        for tag, data in (("eval", eval_data), ("test", test_data)):
+            enc_in, dec_in, target = data[0].to(de), data[1].to(de), data[2].to(de)
+            with torch.no_grad():
+                h = m.get_embedding(enc_in, dec_in)[:, -1, :].contiguous()
+            ranks[tag].append(hip.topk_scores(h, table, 0, 1, param_config.vocab_size - 1, target=target.reshape(-1))[2])
+    host = {kk: torch.cat(v).cpu().numpy() for kk, v in ranks.items()}        # one copy of the ranks for the whole evaluation
+    for k in k_val:
+        for tag in ("eval", "test"):
+            r = host[tag]
+            result[str(k)]["ht_" + tag].append(metrics.hit_at_k_batch(r, k))
+            result[str(k)]["ndcg_" + tag].append(metrics.NDCG_at_k_batch(r, k))
+            result[str(k)]["mrr_" + tag].append(metrics.mrr_at_k_batch(r, k))
+    return result
 
 
 def train(model_train, opt, steps, data, param_config, device_i, neg_sample=True, loss_type="s_soft", opt_type="org",

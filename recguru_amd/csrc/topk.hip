@@ -1,0 +1,403 @@
+// Full-catalogue scoring without the score matrix: per user the K best catalogue rows of h @ table.T and the exact rank of a target
+// among all of them (the inference-side counterpart of full_ce.hip; include/recguru_hip.h, rg_topk_scores).
+//
+//   score(b, i) = h[b] . table[i]   -- ONE function, tk_scores(): a 16 x 16 MFMA tile, users as the A rows, catalogue rows as the B
+//   columns, the k-steps in ascending order.  An output element of the MFMA is a function of its A row and its B column only, so a
+//   score does not depend on the tile, the workgroup, the slice or B that produced it: equal pairs give equal bits, and the top-K
+//   of per-slice top-Ks is the global top-K under one total order.
+//
+// Three kernels, no float atomics (deterministic in both libraries; this unit does not include rg_det.hip.h):
+//   tk_gather_kernel   (target given) one wave per 16 users: the score of (b, target[b]) -> tscore[b], and the number of row b's
+//       exclusion ids (other than the target, inside the catalogue) that score strictly higher -> rank[b] = -that.  A gathered row
+//       goes through tk_scores() as column i of a tile whose diagonal is read.
+//   tk_main_kernel     grid (user blocks of 64, slices).  A wave owns 16 users (h as presplit A operands in registers) and walks the
+//       16-row tiles of its slice, the next tile's rows prefetched into registers.  Per tile: rank[b] += #(score > tscore[b]) (the
+//       target itself scores tscore[b] exactly, excluded ids were subtracted by the gather kernel), and every score packed with its
+//       row into a 64-bit key (score order, then lower row first) is compared with the user's threshold = the worst of its K kept
+//       keys (LDS, owned by the wave: no barrier in the loop).  Keys that pass -- few once the list has warmed up -- are looked up
+//       in the exclusion row (binary search) and inserted one by one: replace the worst, rescan for the new worst (wave-wide).  The
+//       kept set is the K best keys of the slice whatever the insertion order.  Each (slice, user) writes its K keys to the workspace.
+//   tk_merge_kernel    one workgroup per user: bitonic sort of the slices' keys in LDS, the first K decoded to (id, score).
+//
+// Workspace: align256(4 B) + S B K 8 bytes, S = tk_slices(B) = clamp(ceil(1024 / ceil(B / 64)), 1, 64) -- independent of n_rows.
+#include <vector>
+
+#include "rg_common.hip.h"
+#include "../../include/recguru_hip.h"
+
+namespace {
+
+constexpr int TK_WAVES = 4;
+constexpr int TK_THREADS = TK_WAVES * RG_WAVE;
+constexpr int TK_UB = TK_WAVES * 16;        // users per workgroup
+constexpr int TK_MAX_SLICES = 64;
+constexpr int TK_TARGET_WGS = 1024;
+constexpr int TK_MAX_K = 128;
+constexpr int TK_MERGE_THREADS = 256;
+
+typedef unsigned long long tk_key;          // (order-preserving image of the score) << 32 | (0xFFFFFFFF - row in the catalogue); 0 = empty
+
+__device__ __forceinline__ tk_key tk_make_key(float s, unsigned int row) {
+  const unsigned int u = __float_as_uint(s + 0.f);          // -0 -> +0: equal scores, equal images
+  const unsigned int o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((tk_key)o << 32) | (tk_key)(0xFFFFFFFFu - row);
+}
+__device__ __forceinline__ float tk_key_score(tk_key k) {
+  const unsigned int o = (unsigned int)(k >> 32);
+  return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+}
+__device__ __forceinline__ unsigned int tk_key_row(tk_key k) { return 0xFFFFFFFFu - (unsigned int)k; }
+
+__device__ __forceinline__ tk_key tk_readlane(tk_key v, int l) {
+  const unsigned int lo = __builtin_amdgcn_readlane((int)(unsigned int)v, l), hi = __builtin_amdgcn_readlane((int)(unsigned int)(v >> 32), l);
+  return ((tk_key)hi << 32) | lo;
+}
+__device__ __forceinline__ tk_key tk_shfl_xor(tk_key v, int o) {
+  const unsigned int lo = __shfl_xor((int)(unsigned int)v, o), hi = __shfl_xor((int)(unsigned int)(v >> 32), o);
+  return ((tk_key)hi << 32) | lo;
+}
+
+// raw fragment (as loaded) -> MFMA operand: the bf16 tier's is the fragment, the x3 tier's the split pair
+__device__ __forceinline__ void tk_to_op(Frag<__bf16>& o, const Frag<__bf16>& r) { o = r; }
+__device__ __forceinline__ void tk_to_op(FragX3& o, const Frag<x3>& r) { split_x3(r.v, o.hi, o.lo); }
+
+// the score tile: acc reg r of lane (g, i) = A row 4 g + r (a user) . B column i (a catalogue row)
+template <typename T, int KS>
+__device__ __forceinline__ f32x4 tk_scores(const typename OpT<T>::type (&a)[KS], const Frag<T> (&braw)[KS]) {
+  f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    typename OpT<T>::type b;
+    tk_to_op(b, braw[ks]);
+    mma(a[ks], b, acc);
+  }
+  return acc;
+}
+
+// row `row` of src (row < 0: zeros) as the lane's share of KS k-steps
+template <typename T, int D>
+__device__ __forceinline__ void tk_load_row(Frag<T> (&f)[D / 32], const T* __restrict__ src, long long row, int g) {
+#pragma unroll
+  for (int ks = 0; ks < D / 32; ++ks) {
+    if (row >= 0) load_frag(f[ks], src + row * D + ks * 32 + 8 * g);
+    else frag_zero(f[ks]);
+  }
+}
+
+// the wave's 16 users as A operands
+template <typename T, int D>
+__device__ __forceinline__ void tk_load_users(typename OpT<T>::type (&ha)[D / 32], const T* __restrict__ H, long long b, int B, int g) {
+  Frag<T> raw[D / 32];
+  tk_load_row<T, D>(raw, H, b < B ? b : -1, g);
+#pragma unroll
+  for (int ks = 0; ks < D / 32; ++ks) tk_to_op(ha[ks], raw[ks]);
+}
+
+// id in the sorted run ex[lo, hi)?
+__device__ __forceinline__ bool tk_excluded(const int64_t* __restrict__ ex, long long lo, long long hi, long long id) {
+  const long long end = hi;
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    if (ex[mid] < id) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < end && ex[lo] == id;
+}
+
+// ------------------------------------------------------------------------------------------------
+// target scores and the exclusion rows' share of the rank
+// ------------------------------------------------------------------------------------------------
+template <typename T, int D>
+__global__ __launch_bounds__(TK_THREADS) void tk_gather_kernel(rg_topk_args a, float* __restrict__ tscore) {
+  constexpr int KS = D / 32;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, i = lane & 15;
+  const long long ub0 = ((long long)blockIdx.x * TK_WAVES + wave) * 16;
+  if (ub0 >= a.B) return;
+  const T* __restrict__ H = reinterpret_cast<const T*>(a.h);
+  const T* __restrict__ W = reinterpret_cast<const T*>(a.table);
+  typename OpT<T>::type ha[KS];
+  tk_load_users<T, D>(ha, H, ub0 + i, a.B, g);
+
+  // column i of every tile belongs to user ub0 + i
+  const long long b = ub0 + i;
+  const bool bv = b < a.B;
+  const long long row_end = a.first_row + a.n_rows;
+  long long tgt = bv ? (long long)a.target[b] : -1;
+  if (tgt < a.first_row || tgt >= row_end) tgt = -1;          // (the host has refused such a call: never outside the table)
+  long long e0 = 0, len = 0;
+  if (bv && a.excl) {
+    e0 = a.excl_off[b];
+    len = a.excl_off[b + 1] - e0;
+  }
+  long long maxlen = len;
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) {
+    const long long other = __shfl_xor(maxlen, o);
+    maxlen = other > maxlen ? other : maxlen;
+  }
+  float t = 0.f;
+  int higher = 0;
+  for (long long j = 0; j <= maxlen; ++j) {
+    long long id = -1;
+    if (j == 0) id = tgt;
+    else if (j - 1 < len) {
+      id = a.excl[e0 + j - 1];
+      if (id == tgt || id < a.first_row || id >= row_end) id = -1;
+    }
+    Frag<T> wb[KS];
+    tk_load_row<T, D>(wb, W, id, g);
+    const f32x4 acc = tk_scores<T, KS>(ha, wb);
+    // the diagonal element sits in lane (i >> 2, i), reg i & 3: picked with masks (a select chain becomes a jump table whose
+    // accumulator copies sit in front of exec restores -- the build's ISA screen refuses that shape)
+    unsigned int sb = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sb |= __float_as_uint(acc[r]) & (0u - (unsigned int)((i & 3) == r));
+    const float s = __uint_as_float(sb);
+    if (j == 0) t = s;
+    else if (id >= 0 && s > t) ++higher;
+  }
+  if (bv && g == (i >> 2)) {
+    tscore[b] = t;
+    a.rank[b] = -higher;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// the pass over the catalogue
+// ------------------------------------------------------------------------------------------------
+// one key into user list lst[0, K): nothing if it does not beat the worst kept key, else it replaces it (wave-uniform arguments)
+__device__ __forceinline__ void tk_insert(volatile tk_key* lst, int K, volatile tk_key* thr, volatile int* wpos, tk_key ck, int lane) {
+  if (ck <= *thr) return;
+  const int p = *wpos;
+  if (lane == 0) lst[p] = ck;
+  __builtin_amdgcn_wave_barrier();
+  tk_key w = ~0ull;
+  int wp = 0;
+  for (int e = lane; e < K; e += RG_WAVE) {
+    const tk_key v = lst[e];
+    if (v < w) { w = v; wp = e; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const tk_key ow = tk_shfl_xor(w, o);
+    const int op = __shfl_xor(wp, o);
+    if (ow < w || (ow == w && op < wp)) { w = ow; wp = op; }
+  }
+  if (lane == 0) { *thr = w; *wpos = wp; }
+  __builtin_amdgcn_wave_barrier();
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(TK_THREADS) void tk_main_kernel(rg_topk_args a, const float* __restrict__ tscore, tk_key* __restrict__ part,
+                                                             long long tiles_per_slice) {
+  extern __shared__ __align__(16) unsigned char tk_lds[];
+  __shared__ tk_key thr_s[TK_WAVES][16];
+  __shared__ int wpos_s[TK_WAVES][16];
+  constexpr int KS = D / 32;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, i = lane & 15;
+  const int K = a.K;
+  const long long ub0 = ((long long)blockIdx.x * TK_WAVES + wave) * 16;
+  if (ub0 >= a.B) return;                                      // (no workgroup barrier below: the waves are independent)
+  const int slice = blockIdx.y;
+  const bool want_rank = a.rank != nullptr;
+  const T* __restrict__ H = reinterpret_cast<const T*>(a.h);
+  const T* __restrict__ W = reinterpret_cast<const T*>(a.table) + a.first_row * D;
+  volatile tk_key* list = reinterpret_cast<tk_key*>(tk_lds) + (size_t)wave * 16 * K;        // [16][K]
+  volatile tk_key* thr = thr_s[wave];
+  volatile int* wpos = wpos_s[wave];
+  for (int e = lane; e < 16 * K; e += RG_WAVE) list[e] = 0;
+  if (lane < 16) { thr[lane] = 0; wpos[lane] = 0; }
+  __builtin_amdgcn_wave_barrier();
+
+  typename OpT<T>::type ha[KS];
+  tk_load_users<T, D>(ha, H, ub0 + i, a.B, g);
+  // the lane's four users 4 g + r
+  bool uv[4];
+  float t[4];
+  long long e0[4], e1[4];
+  int cnt[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const long long b = ub0 + 4 * g + r;
+    uv[r] = b < a.B;
+    t[r] = (want_rank && uv[r]) ? tscore[b] : INFINITY;
+    e0[r] = (a.excl && uv[r]) ? a.excl_off[b] : 0;
+    e1[r] = (a.excl && uv[r]) ? a.excl_off[b + 1] : 0;
+    cnt[r] = 0;
+  }
+
+  const long long ntiles = (a.n_rows + 15) / 16;
+  const long long tile0 = (long long)slice * tiles_per_slice;
+  const long long tile1 = tile0 + tiles_per_slice < ntiles ? tile0 + tiles_per_slice : ntiles;
+  Frag<T> cur[KS], nxt[KS];
+  if (tile0 < tile1) {
+    const long long row = tile0 * 16 + i;
+    tk_load_row<T, D>(cur, W, row < a.n_rows ? row : -1, g);
+  }
+  for (long long tile = tile0; tile < tile1; ++tile) {
+    if (tile + 1 < tile1) {
+      const long long row = (tile + 1) * 16 + i;
+      tk_load_row<T, D>(nxt, W, row < a.n_rows ? row : -1, g);
+    }
+    const f32x4 acc = tk_scores<T, KS>(ha, cur);
+    const long long row = tile * 16 + i;                       // row in the catalogue (< 2^31)
+    const bool iv = row < a.n_rows;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float s = acc[r];
+      cnt[r] += (iv && s > t[r]) ? 1 : 0;                       // t = +inf: no rank wanted / no such user
+      if (K > 0) {
+        const tk_key key = tk_make_key(s, (unsigned int)row);
+        bool pass = iv && uv[r] && key > thr[4 * g + r];
+        if (pass && a.excl) pass = !tk_excluded(a.excl, e0[r], e1[r], a.first_row + row);
+        unsigned long long m = __ballot(pass);
+        while (m) {
+          const int l = __builtin_amdgcn_readfirstlane(__ffsll((long long)m) - 1);
+          m &= m - 1;
+          const int u = 4 * (l >> 4) + r;
+          tk_insert(list + u * K, K, thr + u, wpos + u, tk_readlane(key, l), lane);
+        }
+      }
+    }
+    if (tile + 1 < tile1) {
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) cur[ks] = nxt[ks];
+    }
+  }
+
+  if (want_rank) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      int c = cnt[r];
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) c += __shfl_xor(c, o);
+      if (i == 0 && uv[r] && c != 0) atomicAdd(a.rank + ub0 + 4 * g + r, c);
+    }
+  }
+  if (K > 0) {
+    for (int e = lane; e < 16 * K; e += RG_WAVE) {
+      const long long b = ub0 + e / K;
+      if (b < a.B) part[((long long)slice * a.B + b) * K + e % K] = list[e];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// merge of the slices' lists, per user
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TK_MERGE_THREADS) void tk_merge_kernel(const tk_key* __restrict__ part, int slices, int B, int K, int n2,
+                                                                    long long first_row, int64_t* __restrict__ ids,
+                                                                    float* __restrict__ scores) {
+  extern __shared__ __align__(16) unsigned char tk_lds[];
+  tk_key* keys = reinterpret_cast<tk_key*>(tk_lds);
+  const int b = blockIdx.x, tid = threadIdx.x;
+  for (int e = tid; e < n2; e += TK_MERGE_THREADS)
+    keys[e] = e < slices * K ? part[((long long)(e / K) * B + b) * K + e % K] : 0;
+  __syncthreads();
+  // bitonic sort, descending
+  for (int k = 2; k <= n2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int e = tid; e < n2; e += TK_MERGE_THREADS) {
+        const int p = e ^ j;
+        if (p > e) {
+          const tk_key x = keys[e], y = keys[p];
+          if (((e & k) == 0) ? x < y : x > y) { keys[e] = y; keys[p] = x; }
+        }
+      }
+      __syncthreads();
+    }
+  for (int e = tid; e < K; e += TK_MERGE_THREADS) {
+    const tk_key k = keys[e];
+    if (ids) ids[(long long)b * K + e] = k ? first_row + (long long)tk_key_row(k) : -1;
+    if (scores) scores[(long long)b * K + e] = k ? tk_key_score(k) : -INFINITY;
+  }
+}
+
+int tk_slices(int B) {
+  const int nub = (B + TK_UB - 1) / TK_UB;
+  const int s = (TK_TARGET_WGS + nub - 1) / nub;
+  return s < 1 ? 1 : (s > TK_MAX_SLICES ? TK_MAX_SLICES : s);
+}
+size_t tk_tscore_bytes(int B) { return ((size_t)B * sizeof(float) + 255) & ~(size_t)255; }
+bool tk_shape_ok(int B, int d, long long n_rows, int K) {
+  return B >= 1 && (d == 64 || d == 128 || d == 256) && K >= 0 && K <= TK_MAX_K && n_rows >= 1 && n_rows < (1LL << 31);
+}
+
+template <typename T, int D>
+int tk_launch(const rg_topk_args& a, hipStream_t s) {
+  float* tscore = reinterpret_cast<float*>(a.workspace);
+  tk_key* part = reinterpret_cast<tk_key*>(reinterpret_cast<unsigned char*>(a.workspace) + tk_tscore_bytes(a.B));
+  const int nub = (a.B + TK_UB - 1) / TK_UB;
+  if (a.rank) hipLaunchKernelGGL((tk_gather_kernel<T, D>), dim3(nub), dim3(TK_THREADS), 0, s, a, tscore);
+  const int slices = tk_slices(a.B);
+  const long long ntiles = (a.n_rows + 15) / 16;
+  const long long tps = (ntiles + slices - 1) / slices;
+  const int used = (int)((ntiles + tps - 1) / tps);            // slices that hold a tile (the others would write empty lists)
+  const size_t lds = (size_t)TK_WAVES * 16 * a.K * sizeof(tk_key);
+  auto k = tk_main_kernel<T, D>;
+  hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(k, dim3(nub, used), dim3(TK_THREADS), lds, s, a, tscore, part, tps);
+  if (a.K > 0) {
+    int n2 = 1;
+    while (n2 < used * a.K) n2 <<= 1;
+    const size_t mlds = (size_t)n2 * sizeof(tk_key);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(tk_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds);
+    hipLaunchKernelGGL(tk_merge_kernel, dim3(a.B), dim3(TK_MERGE_THREADS), mlds, s, part, used, a.B, a.K, n2, a.first_row, a.topk_ids,
+                       a.topk_scores);
+  }
+  RG_CHECK_LAUNCH();
+  return 0;
+}
+
+template <typename T>
+int tk_dispatch(const rg_topk_args& a, hipStream_t s) {
+  switch (a.d) {
+    case 64: return tk_launch<T, 64>(a, s);
+    case 128: return tk_launch<T, 128>(a, s);
+    case 256: return tk_launch<T, 256>(a, s);
+  }
+  return rg_set_error_msg(RG_ERR_UNSUPPORTED, "topk_scores: d must be 64, 128 or 256");
+}
+
+}  // namespace
+
+extern "C" size_t rg_topk_workspace(int B, int d, long long n_rows, int K) {
+  if (!tk_shape_ok(B, d, n_rows, K)) return 0;
+  return tk_tscore_bytes(B) + (size_t)tk_slices(B) * (size_t)B * (size_t)K * sizeof(tk_key);
+}
+
+extern "C" int rg_topk_scores(const rg_topk_args* a, int dtype, void* stream) {
+  static thread_local char msg[200];
+  if (!a || !a->h || !a->table) return rg_set_error_msg(RG_ERR_INVALID, "topk_scores: h and table are required");
+  if (a->B <= 0) return 0;
+  if (dtype != RG_BF16 && dtype != RG_X3) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "topk_scores: dtype must be RG_BF16 or RG_X3");
+  if (a->d != 64 && a->d != 128 && a->d != 256) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "topk_scores: d must be 64, 128 or 256");
+  if (a->K < 0 || a->K > TK_MAX_K) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "topk_scores: K must be in [0, 128]");
+  if (a->n_rows < 1 || a->n_rows >= (1LL << 31) || a->first_row < 0)
+    return rg_set_error_msg(RG_ERR_UNSUPPORTED, "topk_scores: n_rows must be in [1, 2^31) and first_row >= 0");
+  if (a->K > 0 && !a->topk_ids && !a->topk_scores) return rg_set_error_msg(RG_ERR_INVALID, "topk_scores: K > 0 needs topk_ids or topk_scores");
+  if (a->K == 0 && !a->rank) return rg_set_error_msg(RG_ERR_INVALID, "topk_scores: K == 0 needs rank");
+  if (a->rank && !a->target) return rg_set_error_msg(RG_ERR_INVALID, "topk_scores: rank needs target");
+  if ((a->excl == nullptr) != (a->excl_off == nullptr)) return rg_set_error_msg(RG_ERR_INVALID, "topk_scores: excl and excl_off come together");
+  const size_t need = rg_topk_workspace(a->B, a->d, a->n_rows, a->K);
+  if (!a->workspace || a->workspace_bytes < need) {
+    snprintf(msg, sizeof(msg), "topk_scores: workspace of %zu bytes needed, %zu given", need, a->workspace_bytes);
+    return rg_set_error_msg(RG_ERR_INVALID, msg);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (a->rank) {
+    // the targets index the table: checked on the host before anything is launched (one small copy and a wait on the stream)
+    std::vector<long long> tg((size_t)a->B);
+    hipError_t e = hipMemcpyAsync(tg.data(), a->target, sizeof(long long) * (size_t)a->B, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return rg_set_error(e, __func__);
+    for (int b = 0; b < a->B; ++b)
+      if (tg[b] < a->first_row || tg[b] >= a->first_row + a->n_rows) {
+        snprintf(msg, sizeof(msg), "topk_scores: target[%d] = %lld is outside the catalogue rows [%lld, %lld)", b, tg[b], a->first_row,
+                 a->first_row + a->n_rows);
+        return rg_set_error_msg(RG_ERR_UNSUPPORTED, msg);
+      }
+  }
+  if (dtype == RG_BF16) return tk_dispatch<__bf16>(*a, s);
+  return tk_dispatch<x3>(*a, s);
+}

@@ -100,7 +100,8 @@ SYMBOLS = ["rg_last_error", "rg_version", "rg_gemm_nt", "rg_gemm_tn", "rg_attn_f
            "rg_embed_scatter_binned_workspace", "rg_embed_scatter_bwd_binned", "rg_embed_pe_fwd_split", "rg_mse",
            "rg_dropout_gelu", "rg_add_drop_ln", "rg_cross_add_ln", "rg_embed_pe_fwd2",
            "rg_det_enabled", "rg_det_set_arenas", "rg_det_fault",
-           "rg_full_ce_supported", "rg_full_ce_fwd", "rg_full_ce_dw"]
+           "rg_full_ce_supported", "rg_full_ce_fwd", "rg_full_ce_dw",
+           "rg_topk_workspace", "rg_topk_scores"]
 LOSS_SAMPLED_CE, LOSS_BPR, LOSS_BPR_SAS = 0, 1, 2
 c_ll = ctypes.c_longlong
 
@@ -881,6 +882,46 @@ def rank_scores(h, table, target, cand, want_scores=True, want_rank=True):
     a = RankArgs(_p(h), _p(table), _p(target.contiguous()), _p(cand), _p(scores), _p(rank), B, d, C)
     _check(lib().rg_rank_scores(ctypes.byref(a), dt_of(h), _stream()), "rg_rank_scores")
     return scores, rank
+
+
+class TopkArgs(ctypes.Structure):
+    _fields_ = [("h", c_p), ("table", c_p), ("first_row", c_ll), ("n_rows", c_ll), ("target", c_p), ("excl", c_p), ("excl_off", c_p),
+                ("topk_ids", c_p), ("topk_scores", c_p), ("rank", c_p), ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t),
+                ("B", c_i), ("d", c_i), ("K", c_i)]
+
+
+def topk_scores(h, table, k, first_row, n_rows, target=None, excl=None, excl_off=None, want_rank=None):
+    """Full-catalogue scoring of h [B,d] against rows first_row .. first_row + n_rows - 1 of table [rows,d] (rg_topk_scores; the
+    [B, n_rows] scores are never stored): (ids [B,k] int64 | None, scores [B,k] f32 | None, rank [B] int32 | None).  ids: the k best
+    rows not in the user's exclusion run (excl / excl_off: CSR, sorted unique ids), score descending, ties by ascending id, -1 / -inf
+    past the eligible ones; k = 0: rank only.  rank (want_rank, default: target given): rows other than target[b] and outside the
+    exclusion run that score strictly higher than target[b].  f32 tensors take the split-operand form in every f32 tier."""
+    B, d = h.shape
+    k, first_row, n_rows = int(k), int(first_row), int(n_rows)
+    if want_rank is None:
+        want_rank = target is not None
+    assert h.is_contiguous() and table.is_contiguous() and table.dtype == h.dtype and table.shape[1] == d
+    assert 0 <= first_row and first_row + n_rows <= table.shape[0], "the catalogue rows must lie inside the table"
+    assert (excl is None) == (excl_off is None) and (not want_rank or target is not None)
+    if target is not None:
+        assert target.dtype == torch.int64 and target.numel() == B
+        target = target.contiguous()
+    if excl is not None:
+        assert excl.dtype == torch.int64 and excl_off.dtype == torch.int64 and excl_off.numel() == B + 1
+        excl, excl_off = excl.contiguous(), excl_off.contiguous()
+        if excl.numel() == 0:                                               # every row empty (an empty tensor has no address)
+            excl = excl_off = None
+    fn = lib().rg_topk_workspace
+    fn.restype = ctypes.c_size_t
+    need = int(fn(B, d, c_ll(n_rows), k))
+    ws = _tn_workspace(h.device, need, "topk") if need else None           # 0: unsupported shape -- the call below says which
+    ids = torch.empty(B, k, device=h.device, dtype=torch.int64) if k > 0 else None
+    scores = torch.empty(B, k, device=h.device, dtype=torch.float32) if k > 0 else None
+    rank = torch.empty(B, device=h.device, dtype=torch.int32) if want_rank else None
+    a = TopkArgs(_p(h), _p(table), first_row, n_rows, _p(target), _p(excl), _p(excl_off), _p(ids), _p(scores), _p(rank),
+                 _p(ws), need, B, d, k)
+    _check(lib().rg_topk_scores(ctypes.byref(a), _full_ce_code(h), _stream()), "rg_topk_scores")
+    return ids, scores, rank
 
 
 def _i64(t):

@@ -301,6 +301,76 @@ def evaluation_2(model_train, data_loader, de, param, k_val=None, sas=False, dom
     return [result_freq, result_rand]
 
 
+def seen_rows(enc_in, pad_index, eos):
+    """The users' own items as exclusion rows for hip.topk_scores: per row of enc_in [B, L] its ids other than pad and EOS, sorted and
+    unique, as CSR (values [nnz] int64, offsets [B + 1] int64).  Built on the device (one sort, one unique, one bincount)."""
+    B = enc_in.shape[0]
+    rows = torch.arange(B, device=enc_in.device).unsqueeze(1).expand_as(enc_in)
+    keep = (enc_in != pad_index) & (enc_in != eos)
+    key = torch.unique(rows[keep] * (int(eos) + 1) + enc_in[keep])               # sorted by (row, id), duplicates gone
+    off = torch.zeros(B + 1, device=enc_in.device, dtype=torch.int64)
+    off[1:] = torch.cumsum(torch.bincount(torch.div(key, int(eos) + 1, rounding_mode="floor"), minlength=B), 0)
+    return (key % (int(eos) + 1)).contiguous(), off
+
+
+def _catalogue(param, domain):
+    """(first id, number of ids, EOS id): ids 1 .. vocab_size_{a|b} - 1 -- pad (0) and EOS (vocab_size, config.py) are no items."""
+    eos = param.vocab_size_a if domain == "a" else param.vocab_size_b
+    return 1, eos - 1, eos
+
+
+def recommend(model, enc_in, dec_in, k, param, domain="a", device=None, exclude_seen=True, sas=False):
+    """The k items of the whole catalogue that score highest against the last recommender-decoder state: (ids [B, k] int64,
+    scores [B, k] f32), score descending, ties by ascending id; with exclude_seen none of the user's own enc_in items.  One pass
+    over the item table (hip.topk_scores); [B, vocab] is never formed.  Fewer than k eligible items: -1 / -inf fill the row."""
+    if sas:
+        raise NotImplementedError("SASRec scoring is outside the hot path")
+    from . import hip
+    m = _unwrap(model)
+    first, n, eos = _catalogue(param, domain)
+    h = _last_rec_state(model, enc_in, dec_in, domain, param, device)
+    excl, off = seen_rows(enc_in, param.pad_index, eos) if exclude_seen else (None, None)
+    ids, scores, _ = hip.topk_scores(h, ops.shadow(m.item_table(domain)), k, first, n, excl=excl, excl_off=off)
+    return ids, scores
+
+
+def evaluation_full(model_train, data_loader, de, param, k_val=None, domain="a", sas=False):
+    """Unsampled ranking metrics: evaluation_2's loader protocol and eval_steps loop, but the rank of every validation / test target
+    is its exact rank among ALL catalogue items (items scoring strictly higher), counted by the full-catalogue kernel -- the sampled
+    candidate tensors of the batches are ignored.  Returns one result dict in the layout of evaluation_2's."""
+    from . import hip, metrics
+    if sas:
+        raise NotImplementedError("SASRec scoring is outside the hot path")
+    if k_val is None:
+        k_val = [1, 5, 10, 20, 30]
+    model_train.eval()
+    m = _unwrap(model_train)
+    first, n, _ = _catalogue(param, domain)
+    names = ("ht_eval", "ndcg_eval", "mrr_eval", "ht_test", "ndcg_test", "mrr_test")
+    result = {str(k): {nm: [] for nm in names} for k in k_val}
+    ranks = {"eval": [], "test": []}
+    it = iter(data_loader)
+    for _ in range(param.eval_steps):
+        try:
+            eval_data, test_data, _, _ = next(it)
+        except StopIteration:
+            it = iter(data_loader)
+            eval_data, test_data, _, _ = next(it)
+        table = ops.shadow(m.item_table(domain))
+        for tag, data in (("eval", eval_data), ("test", test_data)):
+            enc_in, dec_in, target = data[0].to(de), data[1].to(de), data[2].to(de)
+            h = _last_rec_state(model_train, enc_in, dec_in, domain, param, de)
+            ranks[tag].append(hip.topk_scores(h, table, 0, first, n, target=target.reshape(-1))[2])
+    host = {kk: torch.cat(v).cpu().numpy() for kk, v in ranks.items()}        # one copy of the ranks for the whole evaluation
+    for k in k_val:
+        for tag in ("eval", "test"):
+            r = host[tag]
+            result[str(k)]["ht_" + tag].append(metrics.hit_at_k_batch(r, k))
+            result[str(k)]["ndcg_" + tag].append(metrics.NDCG_at_k_batch(r, k))
+            result[str(k)]["mrr_" + tag].append(metrics.mrr_at_k_batch(r, k))
+    return result
+
+
 def critic_embed(netG, in_seq_a, in_seq_b, param, device):
     """The two no-grad encoder passes of a critic update (gan_training.py:399-411)."""
     with torch.no_grad():
