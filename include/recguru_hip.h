@@ -160,7 +160,11 @@ typedef struct {
   float scale;                /* 1/sqrt(d_k), transformer.py:120 */
   float drop_p; unsigned long long seed;   /* attention-probability dropout, transformer.py:126-127 */
   /* optional [B*L] f32: rows with rowmask == 0 are the padded positions whose layer output the caller multiplies by
-   * the pad mask (transformer.py:594 / :539) -- a 16-query tile made only of such rows is skipped (ctx rows = 0). */
+   * the pad mask (transformer.py:594 / :539) -- a 16-query tile made only of such rows is skipped (ctx rows = 0).
+   * Tiles are counted within a sequence (positions 16 t .. 16 t + 15 of sequence b).  The rows of a skipped tile are
+   * WRITTEN: ctx = 0 and lse = 0, exactly -- a sequence without a live position comes out as all zeros.  A row with
+   * rowmask == 0 that shares its tile with a live row is evaluated like any other row (finite values the caller masks).
+   * Keys are masked by key_ids alone: rowmask never removes a key. */
   const float* rowmask;
   /* x-input form (inference only, lse == NULL): x != NULL replaces qkv by the LAYER INPUT x [B,L,d] and the kernel
    * projects its head's Q, K, V itself with wqkv [3P,d] (rows Q | K | V, torch Linear layout, dtype) and bqkv [3P] f32 --

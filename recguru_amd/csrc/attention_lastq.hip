@@ -34,6 +34,12 @@ template <typename T> struct Row32 {
     for (int k = 0; k < 4; ++k) load_frag(c[k], p + 8 * k);
   }
   __device__ __forceinline__ float at(int j) const { return (float)c[j >> 3].v[j & 7]; }
+  __device__ __forceinline__ void zero() {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) c[k].v[e] = (T)0.f;
+  }
 };
 
 // q . bf16(bias row): what a key of the padded prefix scores (same summation order as the per-key dot products)
@@ -45,6 +51,10 @@ __device__ __forceinline__ float lastq_bias_dot(const float* q, const float* __r
   return d;
 }
 
+// row of K | V that key lane + 64 i is loaded from: keys beyond L at row L - 1 (masked where used), keys of the folded prefix at row
+// `first`, and, when the whole sequence is prefix (first == L), at row L - 1 -- always in bounds
+__device__ __forceinline__ int lastq_row(int lane, int i, int L, int first) { return min(max(min(lane + 64 * i, L - 1), first), L - 1); }
+
 // scores of this lane's keys (raw dot * scale, replaced / -inf where masked), returns the row max.  KPL = keys per
 // lane (64 KPL >= L): a template parameter, so that the loop is straight-line code with clamped, unconditional loads
 template <typename T, int KPL>
@@ -52,12 +62,14 @@ __device__ __forceinline__ float lastq_scores(float (&s)[KPL], const float* q, c
                                               const int64_t* __restrict__ ids, int64_t pad_value, int L, int lane, float scale,
                                               int first, float dzero) {
   // keys before `first` (the sequence's padded prefix, x_masked contract: their K rows all equal the bias row) are not
-  // fetched: their loads are pointed at row `first` (one hot line for all of them) and their dot product is dzero = q . bk
+  // fetched: their loads are pointed at row `first` (one hot line for all of them) and their dot product is dzero = q . bk.
+  // first == L (a sequence without a live position: EVERY key is prefix): the loads stay in bounds at row L - 1, whose data --
+  // possibly unwritten -- is replaced by the selects below
   Row32<T> kr[KPL];
   int64_t id[KPL];
 #pragma unroll
   for (int i = 0; i < KPL; ++i) {
-    const int kc = max(min(lane + 64 * i, L - 1), first);
+    const int kc = lastq_row(lane, i, L, first);
     kr[i].load(kv + (size_t)kc * ldkv + koff);
     id[i] = ids[min(lane + 64 * i, L - 1)];
   }
@@ -88,7 +100,7 @@ __global__ __launch_bounds__(256) void attn_lastq_fwd_kernel(const T* __restrict
   load_row32(q, qlast + (size_t)b * P + h * DK);
   const T* kvb = kv + (size_t)b * L * 2 * P;
   const bool fold = bkv != nullptr && first_live != nullptr;
-  const int first = fold ? min(first_live[b], L - 1) : 0;
+  const int first = fold ? min(first_live[b], L) : 0;
   const float dzero = fold ? lastq_bias_dot<T>(q, bkv + h * DK) : 0.f;
   float s[KPL];
   const float mx = lastq_scores<T, KPL>(s, q, kvb, 2 * P, h * DK, key_ids + (size_t)b * L, pad_value, L, lane, scale, first, dzero);
@@ -107,7 +119,11 @@ __global__ __launch_bounds__(256) void attn_lastq_fwd_kernel(const T* __restrict
   for (int j = 0; j < 32; ++j) o[j] = 0.f;
   Row32<T> vr[KPL];
 #pragma unroll
-  for (int i = 0; i < KPL; ++i) vr[i].load(kvb + (size_t)max(min(lane + 64 * i, L - 1), first) * 2 * P + P + h * DK);
+  for (int i = 0; i < KPL; ++i) vr[i].load(kvb + (size_t)lastq_row(lane, i, L, first) * 2 * P + P + h * DK);
+  if (first >= L) {                                 // (wave-uniform) no live row to point the prefix loads at: 0 * unwritten data must stay 0
+#pragma unroll
+    for (int i = 0; i < KPL; ++i) vr[i].zero();
+  }
   float pz = 0.f;                                   // probability mass of this lane's prefix keys: they all carry V = bv
 #pragma unroll
   for (int i = 0; i < KPL; ++i) {
@@ -139,7 +155,7 @@ __global__ __launch_bounds__(256) void attn_lastq_bwd_kernel(const T* __restrict
   const int b = wg / H, h = wg % H, P = H * DK;
   const unsigned int dbase = (((unsigned int)b * H + h) * L + (L - 1)) * rg_lpad(L);
   const bool fold = bkv != nullptr && first_live != nullptr;
-  const int first = fold ? min(first_live[b], L - 1) : 0;
+  const int first = fold ? min(first_live[b], L) : 0;
   float q[32], g[32];
   load_row32(q, qlast + (size_t)b * P + h * DK);
   load_row32(g, dctx + (size_t)b * P + h * DK);
@@ -162,14 +178,18 @@ __global__ __launch_bounds__(256) void attn_lastq_bwd_kernel(const T* __restrict
   int64_t idk[KPL];
 #pragma unroll
   for (int i = 0; i < KPL; ++i) {               // all V rows, then all K rows and ids: one batch of loads in flight
-    const int kc = max(min(lane + 64 * i, L - 1), first);       // prefix keys: one hot line, data not used (see lastq_scores)
+    const int kc = lastq_row(lane, i, L, first);       // prefix keys: one hot line, data not used (see lastq_scores)
     vr[i].load(kvb + (size_t)kc * 2 * P + P + h * DK);
   }
 #pragma unroll
   for (int i = 0; i < KPL; ++i) {
-    const int kc = max(min(lane + 64 * i, L - 1), first);
+    const int kc = lastq_row(lane, i, L, first);
     kr[i].load(kvb + (size_t)kc * 2 * P + h * DK);
     idk[i] = ids[min(lane + 64 * i, L - 1)];
+  }
+  if (first >= L) {                                 // (wave-uniform) every key is prefix: the K rows only ever meet dsk = 0 (see the forward)
+#pragma unroll
+    for (int i = 0; i < KPL; ++i) kr[i].zero();
   }
 #pragma unroll
   for (int i = 0; i < KPL; ++i) {

@@ -246,6 +246,9 @@ __global__ __launch_bounds__(256, 2) void attn_lastq_x_fwd_kernel(rg_lastq_x_arg
   __bf16* __restrict__ C = reinterpret_cast<__bf16*>(a.ctx);
   // the x rows of a sequence are requested as soon as the previous sequence's last reader of the LDS image is done (one
   // barrier before its epilogue), so the HBM latency runs under the epilogue and the next query's projection
+  // first_live == L (no live position) is clamped to L - 1 ON PURPOSE here: first_row only says where staging starts, and the rows it
+  // then stages are rows of x, which the x_masked contract makes ZERO rows -- never unwritten data (unlike the K | V rows of
+  // csrc/attention_lastq.hip, where the same clamp read an unwritten row).  The other three kernels below use the same rule.
   auto first_row = [&](int b) { return (a.first_live ? min(a.first_live[b], L - 1) : 0) & ~31; };
   // ... and what the next sequence needs from global memory BEFORE its rows land (query, first row) is fetched one stage
   // earlier still and pinned in registers ahead of the request: a load issued after the LDS-DMAs could only be waited

@@ -7,6 +7,10 @@ over RCCL).  Rank 0 writes what the test compares to argv[3].
                                                        tier from RG_DP_TIER (bf16 default): both embedding tables are
                                                        >= 4 MB, so the in-place all-reduce and begin_sync's asynchronous
                                                        exchange run on GPU gradient buffers
+  python tests/dp_worker.py grads wide    <out.npz>    golden case1's model with 8 synthetic users per domain (golden_util.wide_batch): users
+                                                       1, 3, 5, 7 of domain a and user 2 of domain b are all padding in the decoder, so at
+                                                       world 2 rank 1's domain-a shard has a local mask count of 0; tier from RG_DP_TIER
+                                                       (f32 default here); rank r > 0 writes isfinite flags to <out.npz>.rank<r>.npz
   python tests/dp_worker.py curve <fixture> <out.npz>  20 train_recon_x steps + 3 phase-2 iterations, dropout 0, f32 tier
                                                        (RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT from the env)
 """
@@ -62,6 +66,23 @@ def run_steps(z, rank, world, dp, device="cuda"):
         ops.set_compute_dtype(_tier())
         ops.set_data_parallel(dp)
         param, G, D, bt, alpha = bench_case(device)
+    elif isinstance(z, str) and z == "wide":
+        from golden_util import load_case, wide_batch
+        from parity_util import build_cross
+        t = os.environ.get("RG_DP_TIER", "f32")
+        ops.set_compute_dtype("bf16x3" if t == "bf16x3" else (torch.bfloat16 if t == "bf16" else torch.float32))
+        ops.set_data_parallel(dp)
+        zc = load_case("case1")
+        param, G, D = build_cross(zc, device)
+        L = int(zc["meta"][1])
+        bt = wide_batch(param.vocab_size_a - 1, param.vocab_size_b - 1, L, param.n_negs, 8, dead_a=(1, 3, 5, 7), dead_b=(2,))
+        bt = {dom: tuple(t.to(device) for t in bt[dom]) for dom in "ab"}
+        if world == 2:                                         # the point of the case: rank 1's domain-a shard is all padding
+            na = int((bt["a"][2][rank::world] != 0).sum())
+            assert (na == 0) == (rank == 1), "rank %d: local domain-a mask count %d" % (rank, na)
+            assert int((bt["b"][2][rank::world] != 0).sum()) > 0
+        torch.manual_seed(77)
+        alpha = torch.rand(8, 1)
     else:
         from parity_util import batches, build_cross
         ops.set_compute_dtype(torch.float32)
@@ -75,11 +96,16 @@ def run_steps(z, rank, world, dp, device="cuda"):
     real_alpha = T._gp_alpha
     T._gp_alpha = lambda bs, dev: alpha.to(dev)
     try:
-        # bench mode: Adam(D) with lr = 0 -- Adam turns the rounding-level differences between two summation orders of the
-        # discriminator's gradients into different +-lr steps on near-zero-gradient weights, whose bf16 shadows then differ,
-        # and with them the W-loss gradient of the generator; with D held still the generator's gradients of the two runs
-        # are comparable to summation-order accuracy (the exchanged D gradients themselves are compared before the step)
-        return _steps(T, ops, Adam, param, G, D, sh, dp, device, lr_d=0.0 if isinstance(z, str) else 1e-4)
+        # Adam(D) runs with lr = 0 in the two synthetic cases, 1e-4 on a golden case (the exchanged D gradients are read before the step
+        # either way):
+        #   bench: Adam turns the rounding-level differences between two summation orders of the discriminator's gradients into
+        #          different +-lr steps on near-zero-gradient weights, whose bf16 shadows then differ, and with them the W-loss
+        #          gradient of the generator; with D held still the generator's gradients of the two runs are comparable to
+        #          summation-order accuracy
+        #   wide:  the discriminator the generator's W-loss sees stays the golden case's own, so tests/test_dp_hip_gpu.py can hold the
+        #          full batch's gradients to the CPU oracle's _losses(...).backward() on the same weights
+        frozen_d = isinstance(z, str) and z in ("bench", "wide")
+        return _steps(T, ops, Adam, param, G, D, sh, dp, device, lr_d=0.0 if frozen_d else 1e-4)
     finally:
         T._gp_alpha = real_alpha
 
@@ -179,10 +205,15 @@ def main():
         dp.begin_sync = lambda params: None
     if mode == "grads":
         from golden_util import load_case
-        z = what if what == "bench" else load_case(what)
+        z = what if what in ("bench", "wide") else load_case(what)
         dp.start_stats()
         gD, gG, sc = run_steps(z, dp.rank, dp.world, dp, device)
         ex = dp.stop_stats()
+        if dp.rank > 0 and what == "wide":                     # every gradient and logged scalar of the all-padding shard's rank
+            flags = {"D." + k: np.isfinite(v).all() for k, v in gD.items()}
+            flags.update({"G." + k: np.isfinite(v).all() for k, v in gG.items()})
+            np.savez("%s.rank%d.npz" % (out_path, dp.rank), scalars=sc, scalars_finite=np.isfinite(sc),
+                     names=np.array(sorted(flags)), finite=np.array([bool(flags[k]) for k in sorted(flags)]))
         dp.barrier()
         if dp.rank == 0:
             out = {"D." + k: v for k, v in gD.items()}

@@ -58,3 +58,18 @@ def arrays_to_manifest(keys, shapes, ndim):
 def load_case(name):
     z = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
     return {k: z[k] for k in z.files}
+
+
+def wide_batch(V_a, V_b, L, k, n, dead_a=(5,), dead_b=(2,)):
+    """n users per domain at a golden case's shape (L, k, vocabularies V_a / V_b items) from the repo's synthetic generator; the users
+    dead_a of domain a and dead_b of domain b are ALL padding in the decoder (dec_in == dec_out == 0 everywhere: mask count 0), as a user
+    with at most one item is (seq_padding).  {"a" | "b": (enc_in, dec_in, dec_out, n_items)} as CPU tensors."""
+    import torch
+    from recguru_amd import synthetic
+    bt = {}
+    for dom, V, seed, dead in (("a", V_a, 5, dead_a), ("b", V_b, 6, dead_b)):
+        dm = synthetic.make_domain(n, V, L, k, seed=seed, min_len=2)
+        for nm in ("dec_in", "dec_out"):
+            dm[nm][list(dead)] = 0
+        bt[dom] = tuple(torch.as_tensor(dm[nm]) for nm in ("enc_in", "dec_in", "dec_out", "n_items"))
+    return bt

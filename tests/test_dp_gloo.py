@@ -41,14 +41,8 @@ def _losses(p, pD, cfg, O, bt_a, bt_b, count_fn, mean_scale):
 def _wide_batch(cfg, n):
     """n users per domain at the golden case's shape (L, k, vocabularies) from the repo's synthetic generator; user 5 of domain a and
     user 2 of domain b are ALL padding in the decoder (dec_out == 0 everywhere: mask count 0) -- at world 8 a whole shard."""
-    from recguru_amd import synthetic
-    bt = {}
-    for dom, V, seed, dead in (("a", cfg.vocab_size_a - 1, 5, 5), ("b", cfg.vocab_size_b - 1, 6, 2)):
-        dm = synthetic.make_domain(n, V, cfg.L, cfg.n_negs, seed=seed, min_len=2)
-        for nm in ("dec_in", "dec_out"):
-            dm[nm][dead] = 0
-        bt[dom] = tuple(torch.as_tensor(dm[nm]) for nm in ("enc_in", "dec_in", "dec_out", "n_items"))
-    return bt
+    from golden_util import wide_batch
+    return wide_batch(cfg.vocab_size_a - 1, cfg.vocab_size_b - 1, cfg.L, cfg.n_negs, n)
 
 
 def _worker(rank, world, port, ret, n_users):

@@ -92,6 +92,72 @@ def test_dp2_hip_matches_full_batch(name, tmp_path):
     assert np.isfinite(got["scalars"]).all() and np.isfinite(sc).all()
 
 
+_WIDE_FULL = {}
+
+
+def _wide_full_batch(tier, monkeypatch):
+    """The wide full batch through run_steps in one process, once per tier for the tests below (gradients and scalars are not modified by them)."""
+    if tier not in _WIDE_FULL:
+        from dp_worker import run_steps
+        monkeypatch.setenv("RG_DP_TIER", tier)                 # restored to the caller's value by the fixture
+        try:
+            _WIDE_FULL[tier] = run_steps("wide", 0, 1, None)
+        finally:
+            _reset_ops()
+    return _WIDE_FULL[tier]
+
+
+@pytest.mark.parametrize("tier", ["f32", "bf16"])
+def test_dp2_hip_all_padding_shard(tier, tmp_path, monkeypatch):
+    """A whole shard of all-padding decoder rows through the HIP step (dp_worker "wide": 8 users per domain, users 1, 3, 5, 7 of domain a
+    all padding, so rank 1's local domain-a mask count is 0 and only the GLOBAL count keeps its contribution finite): the two ranks'
+    summed gradients equal the single-process full batch's, under the bounds of test_dp2_hip_matches_full_batch (f32) and of
+    test_dp2_hip_bench_shape (bf16); every gradient and logged scalar of rank 1 is finite."""
+    out = os.path.join(str(tmp_path), "rank0.npz")
+    _run_ranks(["grads", "wide", out], world=2, extra_env={"RG_DP_TIER": tier}, timeout=900)
+    got = dict(np.load(out))
+    r1 = np.load(out + ".rank1.npz")
+    assert r1["finite"].all(), [str(n) for n, f in zip(r1["names"], r1["finite"]) if not f]
+    assert r1["scalars_finite"].all(), r1["scalars"]
+    assert len(r1["names"]) > 40
+    gD, gG, sc = _wide_full_batch(tier, monkeypatch)
+    assert np.isfinite(got["scalars"]).all() and np.isfinite(sc).all()
+    bf = tier == "bf16"
+    assert _compare_grads(got, gD, gG, 1e-3 if bf else 1e-4, 1e-4 if bf else 2e-5) > 40
+
+
+def test_wide_full_batch_matches_the_cpu_oracle(monkeypatch):
+    """The anchor of test_dp2_hip_all_padding_shard, same process: the wide FULL batch (five all-padding decoder rows among its 16
+    users) through the shipped step functions, f32 tier, against the CPU oracle's losses and autograd on the same weights and
+    batch (tests/test_dp_gloo.py _losses: both reconstruction losses + the W-loss through the unchanged discriminator).  Bounds of
+    tests/test_parity_gpu.py's f32 tier: losses rtol 1e-3 / atol 1e-5, gradients check_grads' rtol 2e-3, atol 2e-6 + 2e-4 of max."""
+    from golden_util import wide_batch
+    from oracle import recguru_oracle as O
+    from test_dp_gloo import _losses
+    from test_oracle_golden import load
+    gD, gG, sc = _wide_full_batch("f32", monkeypatch)
+    z, cfg, st, _ = load("case1")
+    bt = wide_batch(cfg.vocab_size_a - 1, cfg.vocab_size_b - 1, cfg.L, cfg.n_negs, 8, dead_a=(1, 3, 5, 7), dead_b=(2,))
+    assert int((bt["a"][2][1::2] != 0).sum()) == 0
+    p = O.leafify(st["G"])
+    total = _losses(p, st["D"], cfg, O, bt["a"], bt["b"], lambda c: c, lambda x: x)
+    total.backward()
+    assert np.isfinite(sc).all()
+    np.testing.assert_allclose(float(sc[2] + sc[3] + sc[4]), float(total.detach()), rtol=1e-3, atol=1e-5)
+    for dom, got in (("a", sc[3]), ("b", sc[4])):
+        np.testing.assert_allclose(got, float(O.loss_ae_cross(st["G"], cfg, *bt[dom], domain=dom)), rtol=1e-3, atol=1e-5)
+    n = 0
+    for k, t in p.items():
+        if not t.requires_grad or t.grad is None or k not in gG or any(s in k for s in NOISE):
+            continue
+        ref = t.grad.numpy()
+        assert np.isfinite(gG[k]).all(), k
+        scale = max(float(np.abs(ref).max()), 1e-12)
+        np.testing.assert_allclose(gG[k], ref, rtol=2e-3, atol=2e-6 + 2e-4 * scale, err_msg=k)
+        n += 1
+    assert n > 40
+
+
 @pytest.mark.parametrize("tier", ["bf16", "f32"])
 def test_dp2_hip_bench_shape(tier, tmp_path, capsys):
     """The measured tier under DP at the bench shape (L=200, d=128, N=3, V=100k, k=30; B=16 split 2 x 8): the two 51 MB
