@@ -46,11 +46,27 @@ __global__ __launch_bounds__(SB) void assemble_batch_kernel(const int64_t* __res
   }
 }
 
-__device__ __forceinline__ unsigned int draw32(unsigned long long seed, unsigned long long ctr) {
-  unsigned int lo = (unsigned int)ctr, hi = (unsigned int)(ctr >> 32);
-  unsigned int x = rg_hash((unsigned int)seed, lo);
-  x = rg_hash((unsigned int)(seed >> 32) ^ 0x9E3779B9u, x ^ hi);
-  return x;
+// Counter-based draws: draw32(key, ctr) is a function of (seed, ctr) only.  Both words of the 64-bit seed are folded through a
+// multiplicative mix into TWO round keys (k0: the fold make_drop applies to a dropout seed; k1: a second fold of the high word and
+// k0, so seed -> (k0, k1) is one-to-one) and the counter passes through two rg_hash rounds, one under each key.  A seed that entered
+// as a bare XOR with the counter made the draws of seeds s and s ^ delta permutations of each other (draw(s, c) == draw(s ^ delta,
+// c ^ delta)): every batch of a run then received the same multiset of variates.  tests/sampler_ref.py restates this function.
+struct DrawKey { unsigned int k0, k1; };
+__device__ __forceinline__ DrawKey draw_key(unsigned long long seed) {
+  DrawKey k;
+  k.k0 = make_drop(0.f, seed).seed;
+  unsigned int s = (unsigned int)(seed >> 32) * 0xC2B2AE3Du ^ (k.k0 * 0x27D4EB2Fu + 0x9E3779B9u);
+  s ^= s >> 16; s *= 0x85EBCA6Bu; s ^= s >> 13;
+  k.k1 = s;
+  return k;
+}
+__device__ __forceinline__ unsigned int draw32(const DrawKey& key, unsigned long long ctr) {
+  const unsigned int lo = (unsigned int)ctr, hi = (unsigned int)(ctr >> 32);
+  return rg_hash(key.k1, rg_hash(key.k0, lo) ^ hi);
+}
+// the 64-bit variate of draw i: counters 2i (high word) and 2i + 1 (low word)
+__device__ __forceinline__ unsigned long long draw64(const DrawKey& key, unsigned long long i) {
+  return ((unsigned long long)draw32(key, 2ull * i) << 32) | draw32(key, 2ull * i + 1);
 }
 
 // number of exclusions <= the candidate once shifted: smallest j with ex[j] - j >= u  (ex sorted, unique, in 1..V)
@@ -67,6 +83,7 @@ __global__ __launch_bounds__(SB) void sample_uniform_kernel(const int64_t* __res
                                                            const int64_t* __restrict__ users, int B, int n, int64_t V,
                                                            unsigned long long seed, int64_t* __restrict__ out) {
   const long long total = (long long)B * n;
+  const DrawKey key = draw_key(seed);
   for (long long i = (long long)blockIdx.x * SB + threadIdx.x; i < total; i += (long long)gridDim.x * SB) {
     const int b = (int)(i / n);
     const int64_t usr = users[b];
@@ -74,19 +91,20 @@ __global__ __launch_bounds__(SB) void sample_uniform_kernel(const int64_t* __res
     const int m = (int)(excl_off[usr + 1] - e0);
     const unsigned long long range = (unsigned long long)(V - m);        // allowed items; host guarantees >= 1
     // 64-bit multiply-shift of two hashes: uniform on [0, range) up to 2^-32 relative bias
-    const unsigned long long r = ((unsigned long long)draw32(seed, 2ull * (unsigned long long)i) << 32) | draw32(seed, 2ull * (unsigned long long)i + 1);
-    const int64_t u = (int64_t)__umul64hi(r, range) + 1;                  // 1..range
+    const int64_t u = (int64_t)__umul64hi(draw64(key, (unsigned long long)i), range) + 1;                  // 1..range
     out[i] = nth_allowed(excl + e0, m, u);
   }
 }
 
 // Walker alias draw over ids 0..V (prob[j] = acceptance of slot j, alias[j] its alternative), redrawn while the id is
-// excluded or 0; after 64 rejections falls back to the uniform-over-allowed draw (unreachable in practice).
+// excluded or 0; after 64 rejections falls back to the uniform-over-allowed draw of index i under seed ^ 0xA5A5A5A5 (reached only
+// by a user whose exclusions hold nearly all of the mass; it can return a zero-frequency item).
 __global__ __launch_bounds__(SB) void sample_alias_kernel(const float* __restrict__ prob, const int* __restrict__ alias, int64_t slots,
                                                          const int64_t* __restrict__ excl, const int64_t* __restrict__ excl_off,
                                                          const int64_t* __restrict__ users, int B, int n, int64_t V,
                                                          unsigned long long seed, int64_t* __restrict__ out) {
   const long long total = (long long)B * n;
+  const DrawKey key = draw_key(seed), key_fb = draw_key(seed ^ 0xA5A5A5A5ull);
   for (long long i = (long long)blockIdx.x * SB + threadIdx.x; i < total; i += (long long)gridDim.x * SB) {
     const int b = (int)(i / n);
     const int64_t usr = users[b];
@@ -95,7 +113,7 @@ __global__ __launch_bounds__(SB) void sample_alias_kernel(const float* __restric
     int64_t id = -1;
     for (int tr = 0; tr < 64 && id < 0; ++tr) {
       const unsigned long long c = ((unsigned long long)i * 64ull + tr) * 2ull;
-      const unsigned int h0 = draw32(seed, c), h1 = draw32(seed, c + 1);
+      const unsigned int h0 = draw32(key, c), h1 = draw32(key, c + 1);
       const int64_t slot = (int64_t)(((unsigned long long)h0 * (unsigned long long)slots) >> 32);
       const float f = (float)(h1 >> 8) * (1.f / 16777216.f);
       const int64_t cand = f < prob[slot] ? slot : (int64_t)alias[slot];
@@ -106,8 +124,7 @@ __global__ __launch_bounds__(SB) void sample_alias_kernel(const float* __restric
       id = cand;
     }
     if (id < 0) {
-      const unsigned long long r = ((unsigned long long)draw32(seed ^ 0xA5A5A5A5ull, 2ull * (unsigned long long)i) << 32) | draw32(seed ^ 0xA5A5A5A5ull, 2ull * (unsigned long long)i + 1);
-      id = nth_allowed(excl + e0, m, (int64_t)__umul64hi(r, (unsigned long long)(V - m)) + 1);
+      id = nth_allowed(excl + e0, m, (int64_t)__umul64hi(draw64(key_fb, (unsigned long long)i), (unsigned long long)(V - m)) + 1);
     }
     out[i] = id;
   }

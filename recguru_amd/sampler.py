@@ -9,6 +9,14 @@ does per __getitem__ (the pre-staged TensorLoader keeps one static draw per user
 Quirk Q14: in the reference the loop `for val in seq: weights[seq] = 0` rebinds `val`, so the line
 `weights[val] = 0` zeroes the last sequence item again and the held-out VALIDATION item stays sampleable; only the
 sequence and the test item are excluded.  exclude_val=False (default) reproduces that, True excludes it as well.
+
+The frequency-weighted draw (an alias table over freq^0.75) redraws while the candidate is excluded; a user whose exclusions
+hold nearly all of the mass can fail all 64 tries, and the draw then FALLS BACK to the uniform draw over the user's allowed
+items.  That fall-back can return a zero-frequency item, which torch.multinomial over the weights never would
+(tests/test_sampler_gpu.py pins it as the stated behaviour).
+
+Seeds: every launch takes a 64-bit seed, all of whose bits reach the draws (csrc/sampler.hip draw_key; tests/sampler_ref.py
+restates the draws exactly).  DeviceLoader gives every (loader seed, rank, batch counter) a seed of its own -- batch_seed.
 """
 import numpy as np
 import torch
@@ -31,6 +39,20 @@ def alias_table(p):
         q[l] = q[l] - (1.0 - q[s])
         (small if q[l] < 1.0 else large).append(l)
     return prob.astype(np.float32), alias.astype(np.int32)
+
+
+SEED_BITS, RANK_BITS, COUNTER_BITS = 24, 12, 28
+
+
+def batch_seed(seed, rank, counter):
+    """The 64-bit sampler seed of batch `counter` (= epoch * batches per epoch + batch) of rank `rank` of a DeviceLoader built
+    with `seed`: the three fields side by side, seed << 40 | rank << 28 | counter.  One-to-one on its domain
+    0 <= seed < 2**24, 0 <= rank < 2**12, 0 <= counter < 2**28; outside it two loaders could share a seed, so that is an error."""
+    seed, rank, counter = int(seed), int(rank), int(counter)
+    if not (0 <= seed < 1 << SEED_BITS and 0 <= rank < 1 << RANK_BITS and 0 <= counter < 1 << COUNTER_BITS):
+        raise ValueError("batch_seed: need 0 <= seed < 2**%d, 0 <= rank < 2**%d, 0 <= counter < 2**%d (got %d, %d, %d)"
+                         % (SEED_BITS, RANK_BITS, COUNTER_BITS, seed, rank, counter))
+    return (seed << (RANK_BITS + COUNTER_BITS)) | (rank << COUNTER_BITS) | counter
 
 
 class DeviceDomain(object):
@@ -78,6 +100,8 @@ class DeviceLoader(object):
         self.dom, self.bs, self.Le, self.Ld, self.eos, self.n_neg = domain, batch_size, L_enc, L_dec, eos, n_neg
         self.users = torch.arange(rank, domain.n, world, device=domain.device)[:max(domain.n // world, 1 if world == 1 else 0)]   # equal shards (dist.shard_users)
         self.shuffle, self.seed, self.epoch, self.drop_last = shuffle, int(seed) * 1000003 + rank, 0, drop_last
+        self.seed_rank = (int(seed), int(rank))
+        batch_seed(seed, rank, 0)                            # the domain of the packing, checked up front
         n = self.users.numel()
         self.nb = n // batch_size if drop_last else (n + batch_size - 1) // batch_size
         if self.nb < 1:
@@ -93,7 +117,8 @@ class DeviceLoader(object):
             order = order[torch.randperm(order.numel(), generator=g).to(order.device)]
         for i in range(self.nb):
             u = order[i * self.bs:(i + 1) * self.bs]
-            yield self.dom.batch(u, self.Le, self.Ld, self.eos, self.n_neg, (self.seed << 20) + self.epoch * self.nb + i)
+            yield self.dom.batch(u, self.Le, self.Ld, self.eos, self.n_neg,
+                                 batch_seed(self.seed_rank[0], self.seed_rank[1], self.epoch * self.nb + i))
         self.epoch += 1
 
 
@@ -109,7 +134,9 @@ class DeviceEvalLoader(object):
         self.test_dom = DeviceDomain([list(s) + [int(v)] for s, v in zip(seqs, val)], val, test, V, device,
                                      exclude_val=True)
         self.bs, self.Le, self.Ld, self.eos, self.C, self.seed = batch_size, L_enc, L_dec, eos, candidate_size, int(seed)
-        self.users = torch.arange(rank, len(seqs), world, device=device)     # (evaluation has no collective: every user is scored)
+        self.users = torch.arange(rank, len(seqs), world, device=device)     # (evaluation has no collective: shards may differ in size)
+        # whole batches only, as the reference's DataLoader(drop_last=True) (data_loader.py:477-482): the last
+        # users.numel() % batch_size users are NOT scored; fewer users than one batch give one short batch
         self.nb = max(1, self.users.numel() // batch_size)
         self.epoch = 0
 
