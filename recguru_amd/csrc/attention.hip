@@ -21,13 +21,6 @@
 #define DK 32
 #define NEG_FILL (-1e9f)
 
-#ifdef RG_STAMP
-#define ASTAMP(i) do { unsigned long long t1__ = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-    tacc[i] += t1__ - t0__; t0__ = t1__; } while (0)
-#else
-#define ASTAMP(i)
-#endif
-
 // V operand of O^T = V^T.P^T for the stacked-accumulator slot map: lane (i = dv, g) needs
 // V[key = k0 + 4g + j][dv] (j<4) and V[key = k0 + 16 + 4g + j][dv].
 //  * bf16: V stays ROW-MAJOR in LDS ([key][32+8], filled with raw 16-byte copies) and the gfx950
@@ -249,10 +242,6 @@ __device__ __forceinline__ void and_op(Frag<float>& f, const uint2& m0, const ui
 // HM: head-major qkv (rg_attn_args.qkv_hm; bf16): a head's K / V / Q tiles are contiguous runs, K and V arrive by LDS-DMA.
 template <typename T, int NKT, bool CAUSAL, int DM, bool XIN = false, bool HM = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(rg_attn_args a) {
-#ifdef RG_STAMP
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long t0__ = __builtin_amdgcn_s_memtime();
-#endif
   constexpr int LPK = NKT * 16;       // padded key count (multiple of 32)
   // K rows [key][dk].  bf16: 64-byte rows, no pad, the four 16-byte chunks of a row XOR-swizzled by f(row) =
   // -(row >> 2) & 3: the ds_read_b128 fragment reads (lane (li, lg): chunk lg of row li) are conflict-free under the
@@ -394,9 +383,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(rg_attn_args a) {
   }
   // the head's dropout words: hashed HERE, under the latency of the mask / key-id loads above (at the top of the kernel,
   // with nothing in flight, the fill was exposed time: 1 us per head)
-#ifndef RG_ABL_NO_DMASK    // (timing-only ablation: the per-head hash of the dropout words)
   if constexpr (DM == 1) fill_dmask<NW, LPK>(dmask, drop, b, h, a.H, L, tid, first_q & ~15);
-#endif
   unsigned int wl = 0u;                            // bit i: tile wave + 4 i is live
 #pragma unroll
   for (int rd = 0; rd < NRD; ++rd) {
@@ -596,7 +583,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(rg_attn_args a) {
   const int klo = klo_s;
   const int nz = zkeys ? (__builtin_amdgcn_readfirstlane(zpre_s) >> 4) : 0;        // leading key tiles made of zero-input keys only
   const int nskip = nz >= 2 ? (nz - 1) * 16 : 0;   // keys of tiles 1 .. nz-1, folded into key 0
-  ASTAMP(0);
 
   // scores stay RAW dot products; the reference's 1/sqrt(d_k) and log2(e) are folded into the exp2 argument
   const float c2 = a.scale * 1.4426950408889634f;
@@ -674,7 +660,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(rg_attn_args a) {
             else body(std::false_type{});
           }
       }
-      ASTAMP(1);
       mx = fmaxf(mx, __shfl_xor(mx, 16));
       mx = fmaxf(mx, __shfl_xor(mx, 32));
       const float nmx = -mx * c2;
@@ -747,7 +732,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(rg_attn_args a) {
           __builtin_amdgcn_sched_barrier(0);        // one pair's hashes at a time (all of them in flight cost a wave per SIMD)
         }
       }
-      ASTAMP(2);
       o[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; o[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
       f32x4 osum = (f32x4){0.f, 0.f, 0.f, 0.f};
       Frag<E> ones;
@@ -795,7 +779,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(rg_attn_args a) {
     }
     float inv = __builtin_amdgcn_rcpf(sum);
     if constexpr (DM == 1) inv *= drop.inv_keep;       // dropped entries were ANDed to zero, the 1/(1-p) rides on the normaliser
-    ASTAMP(3);
     if (q < L) {
       T* __restrict__ ctx = reinterpret_cast<T*>(a.ctx) + ((size_t)b * L + q) * P + h * DK;
 #pragma unroll
@@ -805,11 +788,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(rg_attn_args a) {
         for (int r = 0; r < 4; ++r) v[r] = o[dt][r] * inv;
         store4(ctx + dt * 16 + 4 * lg, v);
       }
-#ifndef RG_STAMP
       if (lg == 0 && a.lse) a.lse[((size_t)b * a.H + h) * L + q] = (mx < 0.5f * MASK_BIG ? NEG_FILL : mx * a.scale) + __logf(sum);
-#endif
     }
-    ASTAMP(4);
   }
   // rows of this wave's padded tiles: context = 0 (finite placeholders for a backward that never reads them); last,
   // so that no load of the loop above waits behind these stores
@@ -821,17 +801,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(rg_attn_args a) {
       const float z4[4] = {0.f, 0.f, 0.f, 0.f};
       store4(ctxz + 4 * lg, z4);
       store4(ctxz + 16 + 4 * lg, z4);
-#ifndef RG_STAMP
       if (lg == 0 && a.lse) a.lse[((size_t)b * a.H + h) * L + q] = 0.f;
-#endif
     }
   }
-#ifdef RG_STAMP
-  if (a.lse != nullptr && blockIdx.x >= 8192 && blockIdx.x < 9216 && lane == 0) {   // diagnostic build: lse doubles as the stamp buffer (steady-state window)
-    unsigned long long* dbg = reinterpret_cast<unsigned long long*>(a.lse) + (size_t)((blockIdx.x - 8192) * 4 + wave) * 8;
-    for (int i = 0; i < 8; ++i) dbg[i] = tacc[i];
-  }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1393,7 +1365,6 @@ __global__ __launch_bounds__(NTH, NTH == 512 ? 1 : 2) void attn_bwd_bf16_kernel(
         mma(gtf, pf, dvt[dt]);     // dV^T[dv][key] += sum_q dO[q][dv] P[q][key]
         mma(qtf, dsf, dkt[dt]);    // dK^T[dk][key] += sum_q Q[q][dk] dS[q][key]
       }
-#ifndef RG_ABL_NO_DS      // (timing-only ablation, tools/ab_round5.sh: the whole in-sweep dQ path -- dS scratch write, transposing read, 16-deep MFMAs)
       if constexpr (ONEPASS) {
         // dS[q][key] (accumulator layout: lane = key, registers = 4 queries) -> bf16 -> the wave's scratch tile
         // T[key][q] in the pad columns (32..39) of ITS rows of Qs (q 0..7) and Ks (q 8..15), one 8-byte store per
@@ -1418,7 +1389,6 @@ __global__ __launch_bounds__(NTH, NTH == 512 ? 1 : 2) void attn_bwd_bf16_kernel(
         }
         asm volatile("" ::: "memory");
       }
-#endif
     };
     if constexpr (ONEPASS) {
 #pragma unroll
@@ -1679,82 +1649,50 @@ static int launch_bwd(const rg_attn_bwd_args& a, hipStream_t s) {
     else if (nkt <= 14) RG_BWD16(14);
     else if (nkt <= 16) RG_BWD16(16);
     else if (nkt <= 26) {
-      // 26 key tiles: 161 KB of LDS = one workgroup per CU -- with eight waves (RG_ATTN_BWD_256=1: the four-wave form, for A/B)
-      static const bool four = getenv("RG_ATTN_BWD_256") != nullptr;
-      if (four) RG_BWD16(26);
-      else {
-        const dim3 block8(512);
+      // 26 key tiles: 161 KB of LDS = one workgroup per CU -- with eight waves (the four-wave form was measured, removed: DESIGN.md 6a)
+      const dim3 block8(512);
 #define RG_BWD26(C)                                                                                          \
   do {                                                                                                       \
     if (dm == 0) hipLaunchKernelGGL((attn_bwd_bf16_kernel<26, C, 0, false, 512>), grid, block8, 0, s, a);      \
     else if (dm == 1) hipLaunchKernelGGL((attn_bwd_bf16_kernel<26, C, 1, false, 512>), grid, block8, 0, s, a); \
     else hipLaunchKernelGGL((attn_bwd_bf16_kernel<26, C, 2, false, 512>), grid, block8, 0, s, a);              \
   } while (0)
-        if (a.causal) RG_BWD26(true);
-        else RG_BWD26(false);
+      if (a.causal) RG_BWD26(true);
+      else RG_BWD26(false);
 #undef RG_BWD26
-      }
     } else return rg_set_error_msg(RG_ERR_UNSUPPORTED, "attn_bwd: L > 416 not supported yet");
 #undef RG_BWD16
 #undef RG_BWD16_2
   } else {
     if constexpr (std::is_same<T, x3>::value) {
-      // bf16x3, 128 < L <= 224 (round 5): the two-tiles-at-a-time form (RESTAGE) -- its 81.6 KB of LDS let TWO workgroups share a CU
+      // bf16x3, L <= 128: the four-tile form -- K, V, Q, dO of the head as split tiles in LDS (16 key tiles would be 168 KB -- beyond a CU's LDS).
+      // 128 < L <= 224 (round 5): the two-tiles-at-a-time form (RESTAGE) -- its 81.6 KB of LDS let TWO workgroups share a CU
       // (four waves per SIMD) where the four-tile form's 153 KB allow one: 18.9 -> 14.9 ms per bench-shape step
-      // (profiles/r05/ab/bench_bf16x3_attention_backward_*.json); RG_ATTN_BWD_X3_NO_RESTAGE=1: the four-tile form (A/B)
-      static const bool restage_short = getenv("RG_ATTN_BWD_X3_NO_RESTAGE") == nullptr;
-      if (nkt > 8 && nkt <= 14 && !a.qkv_hm && restage_short) {
+      // (profiles/r05/ab/bench_bf16x3_attention_backward_*.json; the four-tile form at these lengths was measured, removed: DESIGN.md 6a).
+      // 224 < L <= 416 (round 5): the same kernel with two of the four split tiles resident at a time (the generic two-image kernel
+      // below was measured at these lengths, removed as a route: DESIGN.md 6a)
+      if (nkt <= 26 && !a.qkv_hm) {
         const int dm = a.drop_p <= 0.f ? 0 : (a.drop_p == 0.5f ? 1 : 2);
         const dim3 block8(512);
-#define RG_BWDS2(C)                                                                                                      \
-  do {                                                                                                                  \
-    if (dm == 0) hipLaunchKernelGGL((attn_bwd_bf16_kernel<14, C, 0, false, 512, x3, true>), grid, block8, 0, s, a);       \
-    else if (dm == 1) hipLaunchKernelGGL((attn_bwd_bf16_kernel<14, C, 1, false, 512, x3, true>), grid, block8, 0, s, a);  \
-    else hipLaunchKernelGGL((attn_bwd_bf16_kernel<14, C, 2, false, 512, x3, true>), grid, block8, 0, s, a);               \
+#define RG_BWDX2(N, C, R)                                                                                          \
+  do {                                                                                                             \
+    if (dm == 0) hipLaunchKernelGGL((attn_bwd_bf16_kernel<N, C, 0, false, 512, x3, R>), grid, block8, 0, s, a);      \
+    else if (dm == 1) hipLaunchKernelGGL((attn_bwd_bf16_kernel<N, C, 1, false, 512, x3, R>), grid, block8, 0, s, a); \
+    else hipLaunchKernelGGL((attn_bwd_bf16_kernel<N, C, 2, false, 512, x3, R>), grid, block8, 0, s, a);              \
   } while (0)
-        if (a.causal) RG_BWDS2(true); else RG_BWDS2(false);
-#undef RG_BWDS2
-        RG_CHECK_LAUNCH();
-        return 0;
-      }
-      if (nkt <= 14 && !a.qkv_hm) {            // (16 key tiles: 168 KB of split tiles -- beyond a CU's LDS; the generic form below)
-        const int dm = a.drop_p <= 0.f ? 0 : (a.drop_p == 0.5f ? 1 : 2);
-        const dim3 block8(512);
-#define RG_BWDX2(N, C)                                                                                            \
-  do {                                                                                                            \
-    if (dm == 0) hipLaunchKernelGGL((attn_bwd_bf16_kernel<N, C, 0, false, 512, x3>), grid, block8, 0, s, a);        \
-    else if (dm == 1) hipLaunchKernelGGL((attn_bwd_bf16_kernel<N, C, 1, false, 512, x3>), grid, block8, 0, s, a);   \
-    else hipLaunchKernelGGL((attn_bwd_bf16_kernel<N, C, 2, false, 512, x3>), grid, block8, 0, s, a);                \
+#define RG_BWDX(N, R)                        \
+  do {                                       \
+    if (a.causal) RG_BWDX2(N, true, R);      \
+    else RG_BWDX2(N, false, R);              \
   } while (0)
-#define RG_BWDX(N)                        \
-  do {                                    \
-    if (a.causal) RG_BWDX2(N, true);      \
-    else RG_BWDX2(N, false);              \
-  } while (0)
-        if (nkt <= 2) RG_BWDX(2);
-        else if (nkt <= 4) RG_BWDX(4);
-        else if (nkt <= 8) RG_BWDX(8);
-        else RG_BWDX(14);
+        if (nkt <= 2) RG_BWDX(2, false);
+        else if (nkt <= 4) RG_BWDX(4, false);
+        else if (nkt <= 8) RG_BWDX(8, false);
+        else if (nkt <= 14) RG_BWDX(14, true);
+        else if (nkt <= 16) RG_BWDX(16, true);
+        else RG_BWDX(26, true);
 #undef RG_BWDX
 #undef RG_BWDX2
-        RG_CHECK_LAUNCH();
-        return 0;
-      }
-      // bf16x3, 224 < L <= 416 (round 5): the same kernel with two of the four split tiles resident at a time (RESTAGE);
-      // RG_ATTN_BWD_X3_GENERIC=1: the generic two-image kernel below (A/B)
-      static const bool generic_long = getenv("RG_ATTN_BWD_X3_GENERIC") != nullptr;
-      if (nkt <= 26 && !a.qkv_hm && !generic_long) {
-        const int dm = a.drop_p <= 0.f ? 0 : (a.drop_p == 0.5f ? 1 : 2);
-        const dim3 block8(512);
-#define RG_BWDR2(N, C)                                                                                                  \
-  do {                                                                                                                  \
-    if (dm == 0) hipLaunchKernelGGL((attn_bwd_bf16_kernel<N, C, 0, false, 512, x3, true>), grid, block8, 0, s, a);        \
-    else if (dm == 1) hipLaunchKernelGGL((attn_bwd_bf16_kernel<N, C, 1, false, 512, x3, true>), grid, block8, 0, s, a);   \
-    else hipLaunchKernelGGL((attn_bwd_bf16_kernel<N, C, 2, false, 512, x3, true>), grid, block8, 0, s, a);                \
-  } while (0)
-        if (nkt <= 16) { if (a.causal) RG_BWDR2(16, true); else RG_BWDR2(16, false); }
-        else { if (a.causal) RG_BWDR2(26, true); else RG_BWDR2(26, false); }
-#undef RG_BWDR2
         RG_CHECK_LAUNCH();
         return 0;
       }

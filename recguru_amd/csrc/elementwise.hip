@@ -137,7 +137,7 @@ __global__ __launch_bounds__(EW_BLOCK) void embed_pe_fwd_rows_kernel(const T* __
 // the real 56 %-live mask).  Here a wave owns RPW consecutive POSITIONS (lane group lr: position pos0 + lr) and walks a range of
 // sequences b, U of them in flight: its positional rows are read ONCE into 8 registers per lane and reused for every sequence; the row
 // loads are unconditional (a padded position reads row 0 of the table, one hot line set, and its result is discarded); the output rows
-// leave by nontemporal stores when NT (the launcher's choice, RG_EMBED_NT).  Consecutive waves take consecutive position blocks of the same
+// leave by nontemporal stores when NT (the launcher's choice, by size).  Consecutive waves take consecutive position blocks of the same
 // sequence range, so the 32-B id / 16-B mask pieces of neighbouring waves share cache lines and a workgroup writes 4 KiB runs.
 template <typename T> __device__ __forceinline__ void store8_nt(T* p, const float* v);
 template <> __device__ __forceinline__ void store8_nt<float>(float* p, const float* v) {
@@ -1287,21 +1287,18 @@ extern "C" int rg_cross_rows(const float* s, const float* oh, const float* bo, f
 
 static int embed_pe_fwd_launch(const void* table, const float* pe, const int64_t* ids, const float* mask, void* out, void* out2,
                                long long ntok, int L, int d, const DropCfg& drop, int dtype, hipStream_t s, long long table_rows = 0) {
-  // The row form is selected for the two-output call and by RG_EMBED_ROWS=1 (A/B).  Measured (round 5, bench shape, 56 % live
-  // positions): 41 vs 49 us per launch when the same launch is repeated (ids / mask / table hot), 78.0 vs 77.0 us INSIDE the step --
-  // both kernels sit at the memory system's rate for this read / write mix (0.55 of 8 TB/s = 0.89 of the box's measured copy rate),
-  // so the simpler element-per-thread kernel stays the default.
-  static const int rows_form = getenv("RG_EMBED_ROWS") ? atoi(getenv("RG_EMBED_ROWS")) : 0;
-  // RG_EMBED_FORM: 2 = position-major (default since round 6), 0 = the element-per-thread kernel; RG_EMBED_NT: 1 = nontemporal stores
-  static const int form = getenv("RG_EMBED_FORM") ? atoi(getenv("RG_EMBED_FORM")) : 2;
+  // Three forms: position-major (one output, d 128 / 256, whole sequences), the row form (the two-output call), element-per-thread (the rest).
+  // Position-major has been the default since round 6 (profiles/r06/ab/embed_forms.txt).  The row form against the
+  // element-per-thread kernel for ONE output was measured (round 5, bench shape, 56 % live positions): 41 vs 49 us per launch when the same
+  // launch is repeated (ids / mask / table hot), 78.0 vs 77.0 us INSIDE the step -- both kernels sit at the memory system's rate for this
+  // read / write mix (0.55 of 8 TB/s = 0.89 of the box's measured copy rate); that route was removed.
   // Store policy (measured, profiles/r06/ab/embed_forms.txt): with the bench table (25.6 MB) and its 210 MB of output rows the Infinity Cache
   // (256 MB) absorbs ordinary stores -- 68.5 us per launch in the step against 73.0 with nontemporal ones --, with the 1 GiB config-5 table it
   // cannot, and ordinary stores cost the gather its cache: 92.8 -> 78.3 us (uniform ids), 63.4 -> 48.6 (Zipf, 44 % padded).  So: nontemporal
-  // stores when table + output rows exceed the Infinity Cache (table_rows = 0: unknown, the output alone decides); RG_EMBED_NT=0/1 forces.
-  static const int nt_env = getenv("RG_EMBED_NT") ? atoi(getenv("RG_EMBED_NT")) : -1;
+  // stores when table + output rows exceed the Infinity Cache (table_rows = 0: unknown, the output alone decides).
   const long long esz = dtype == RG_BF16 ? 2 : 4;
-  const int use_nt = nt_env >= 0 ? nt_env : ((table_rows + ntok) * d * esz > (256ll << 20) ? 1 : 0);
-  if (form == 2 && !rows_form && !out2 && (d == 128 || d == 256) && L > 0 && ntok % L == 0 && ntok < (1ll << 31) / d) {
+  const bool use_nt = (table_rows + ntok) * d * esz > (256ll << 20);
+  if (!out2 && (d == 128 || d == 256) && L > 0 && ntok % L == 0 && ntok < (1ll << 31) / d) {
     // waves = position blocks x sequence ranges; the ranges sized so that the launch is ~ 8 workgroups (32 waves) per CU, every wave
     // with the same number of sequences
     const int B = (int)(ntok / L), rpw = 64 / (d / 8), npb = (L + rpw - 1) / rpw;
@@ -1320,14 +1317,14 @@ static int embed_pe_fwd_launch(const void* table, const float* pe, const int64_t
 #undef RG_EMBP_T
 #undef RG_EMBP
   }
-  if ((d == 128 || d == 256) && L > 0 && ntok < (1ll << 31) / d && (rows_form || out2)) {
+  if (out2 && (d == 128 || d == 256) && L > 0 && ntok < (1ll << 31) / d) {
     // one wave per 64-token block, at most 8 workgroups (32 waves) per CU -- and every wave the SAME number of blocks: with 12 800
     // blocks on 8 192 waves a third of the waves took two blocks and the launch lasted two block times for 1.56 of work
     const long long nblk = (ntok + 63) / 64, cap = 256LL * 8 * (EW_BLOCK / 64);
     const long long iters = (nblk + cap - 1) / cap, waves = (nblk + iters - 1) / iters;
     const int grid = (int)((waves + EW_BLOCK / 64 - 1) / (EW_BLOCK / 64));
-#define RG_EMB(T, D, M2) hipLaunchKernelGGL((embed_pe_fwd_rows_kernel<T, D, 4, M2>), dim3(grid), dim3(EW_BLOCK), 0, s, (const T*)table, pe, ids, mask, (T*)out, (__bf16*)out2, (int)ntok, L, drop)
-#define RG_EMB_T(T) do { if (d == 128) { if (out2) RG_EMB(T, 128, true); else RG_EMB(T, 128, false); } else { if (out2) RG_EMB(T, 256, true); else RG_EMB(T, 256, false); } } while (0)
+#define RG_EMB(T, D) hipLaunchKernelGGL((embed_pe_fwd_rows_kernel<T, D, 4, true>), dim3(grid), dim3(EW_BLOCK), 0, s, (const T*)table, pe, ids, mask, (T*)out, (__bf16*)out2, (int)ntok, L, drop)
+#define RG_EMB_T(T) do { if (d == 128) RG_EMB(T, 128); else RG_EMB(T, 256); } while (0)
     DISPATCH_T(dtype, RG_EMB_T(__bf16), RG_EMB_T(float), "embed_pe_fwd")
 #undef RG_EMB_T
 #undef RG_EMB

@@ -295,12 +295,6 @@ __device__ __forceinline__ void zero_to_hbm(T* __restrict__ dst, int ld, int col
   }
 }
 
-#ifdef RG_STAMP
-#define STAMP(i) do { unsigned long long t1__ = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-    tacc[i] += t1__ - t0__; t0__ = t1__; } while (0)
-#else
-#define STAMP(i)
-#endif
 
 // DM: dropout mode -- 0 none, 1 p == 0.5 (one hash bit per element), 2 generic p (16-bit hash fields)
 // CROSS: the decoder form (collapsed cross-attention stage between the two LayerNorms).  The encoder launches (three
@@ -312,22 +306,19 @@ __device__ __forceinline__ void zero_to_hbm(T* __restrict__ dst, int ld, int col
 // RT: 16-row tiles per work tile -- 4 (64 tokens) or 2 (32 tokens: half the accumulators and activation tiles per workgroup,
 // so that three to four workgroups share a CU instead of two; the per-phase stamps show a wave at 2 per SIMD spending its
 // time on exposed LDS / VALU latencies, not on the matrix pipe or the weight stream)
-// PIPE (round 5; bf16, no saves, no cross stage, d_ff >= 256): the FFN chunk loop software-pipelined -- see the loop.
+// (round 5, measured and NOT kept, removed: the FFN chunk loop software-pipelined for the bf16 inference launch -- the second product of
+// chunk ch - 1 interleaved with the dropout + GELU epilogue of chunk ch, bit-identical, 0 ... 3 % SLOWER: matrix and vector cycles largely
+// ADD on a gfx950 SIMD, whatever their order.  DESIGN.md 6a, profiles/r05/ab/post_attn_pipelined_ffn.txt.)
 // (round 6, measured and NOT kept: this kernel alone without packed-f32 VALU instructions via the per-function target feature
 // `__attribute__((target("no-packed-fp32-ops")))`.  The whole-library variant had shown the fused block 2 % faster and ffn_bwd_data 2 % slower
 // (profiles/r06/ab/nopk_*); with the attribute on this kernel only, the always-inline device helpers -- compiled with the feature -- are no
 // longer inline-compatible with it and become CALLS: 276 -> 605 us per inference launch, step 56.4 -> 70.0 ms, outputs bit-identical.)
-template <typename T, int DM, bool CROSS, bool SAVE, bool RES = false, int RT = 4, bool PIPE = false>
+template <typename T, int DM, bool CROSS, bool SAVE, bool RES = false, int RT = 4>
 __global__ __launch_bounds__(256, (sizeof(T) == 2 ? (RT == 2 ? 3 : 2) : ((std::is_same<T, x3>::value && RT == 2) ? 2 : 1)))
 void post_attn_fwd_kernel(rg_post_attn_args a) {
-  static_assert(!PIPE || (sizeof(T) == 2 && !SAVE && !CROSS && !RES && RT == 4), "PIPE: the bf16 inference launch");
   constexpr int FTM = 16 * RT;        // tokens per work tile
   constexpr int PL = FTM * FD * 2;    // bf16x3: bytes between the hi and the lo tile
   typedef typename LdsT<T, PL>::type LT;  // element type of the LDS tiles (T, or x3p: a hi and a lo bf16 tile)
-#ifdef RG_STAMP
-  unsigned long long tacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long t0__ = __builtin_amdgcn_s_memtime();
-#endif
   // LDS: ctx tile (later: out staging) | x tile (later: g chunk) | y tile | params | row-stat exchange | [h1 chunk]
   constexpr int ACT_BYTES = FTM * Tile<LT>::LD * (int)sizeof(LT) * LdsT<T, PL>::PLANES;
   extern __shared__ __align__(16) unsigned char smem[];
@@ -464,7 +455,6 @@ void post_attn_fwd_kernel(rg_post_attn_args a) {
       continue;
     }
     lds_barrier();
-    STAMP(0);
     // ---- attention output projection (weights already in wp), bias folded into the accumulators
     f32x4 acc[2][RT];
     init_acc(acc, p_bo, n0, lg);
@@ -473,7 +463,6 @@ void post_attn_fwd_kernel(rg_post_attn_args a) {
     // + residual x (from LDS), LayerNorm 1 on the registers
     add_tile<XT>(acc, Ax, n0, li, lg);
     if constexpr (RES) add_tile<LT>(acc, Ay, n0, li, lg);          // x_lo
-    STAMP(1);
     float rstd[RT];
     ln_regs<RT, KEEPY>(acc, rstd, p_g1, p_be1, redA, redB, a.eps, n0, wave, li, lg);
     // (past the barrier inside ln_regs every wave is done with the ctx tile, x and x_lo)
@@ -484,7 +473,6 @@ void post_attn_fwd_kernel(rg_post_attn_args a) {
         if (mb[rt] + li < a.M) rstd1o[mb[rt] + li] = rstd[rt];
     }
     regs_to_tile<LT>(acc, Ay, n0, li, lg);
-    STAMP(2);
     if constexpr (CROSS) {
       // collapsed decoder cross-attention: y2 = LayerNorm(y1 + o[b]); y1 is saved from its tile first
       if (ysave) { lds_barrier(); tile_to_hbm<T, true>(Ay, ysave, FD, 0, mb, a.M, tid); }
@@ -573,7 +561,6 @@ void post_attn_fwd_kernel(rg_post_attn_args a) {
       constexpr bool cross = CROSS;
       if (cross ? (y2save != nullptr) : (ysave != nullptr)) tile_to_hbm<T, true>(Ay, cross ? y2save : ysave, FD, 0, mb, a.M, tid);
     }
-    STAMP(3);
     // word index of this lane ROW's row tile (row tile lg, row li) in the two dropout index spaces: (row * d_ff + column) >> 5 with
     // column = chunk * 128 + 32 * wave + 4 lg + j (j < 20) and (row * 128 + 32 * wave + 4 lg + j) >> 5
     // (bf16 kernels only: in the f32-storage kernels hipcc turns the select over lg into lane-divergent branches whose results pass through
@@ -589,121 +576,6 @@ void post_attn_fwd_kernel(rg_post_attn_args a) {
     // ---- FFN: stream d_ff in 128-wide chunks; the second GEMM accumulates across chunks
     f32x4 acc2[2][RT];
     init_acc(acc2, p_b2, n0, lg);
-    if constexpr (PIPE) {
-      // Software-pipelined form (MEASURED: no gain -- see the end of this comment).  In the plain loop below a wave alternates between a matrix phase (32 MFMAs) and a VALU phase
-      // (dropout + GELU of 32 elements per lane: ~260 VALU instructions, 64 of them half-rate transcendentals) with a barrier between them, so
-      // the matrix pipe idles through every VALU phase of the wave and the counters show the two waves of a SIMD adding their
-      // phases up rather than overlapping them (SQ_VALU_MFMA_COEXEC_CYCLES = 14 % of the matrix pipe's busy cycles).  Here the
-      // product that does NOT depend on the current epilogue -- out += g(ch - 1) W2 (g chunks alternate between the x tile and the ctx
-      // tile, both free during the FFN) -- sits in the SAME straight-line block as the epilogue of chunk ch, where the scheduler
-      // interleaves them.  (h1 of chunk ch + 1 into a second accumulator set as well: 256 VGPRs with 66 - 84 spilled; not kept.)
-      // Outcome at the bench shape (profiles/r05/ab/post_attn_pipelined_ffn.txt): left to the scheduler the matrix instructions
-      // all moved to the front of the block (no change, 10.9 -> 11.0 ms per step); in eight slices of 4 MFMAs + one epilogue piece
-      // 10.9 -> 10.95; one MFMA per half GELU pair (this code) 10.9 -> 11.2.  The matrix pipe's 21 % of the SIMD time is not what
-      // the kernel waits for in particular: matrix and vector cycles largely ADD on a gfx950 SIMD (tools/peaks.hip: one MFMA hides ~4
-      // cycles of the same wave's VALU work, 44 % of its own cycles with a second wave) -- ~196 full-rate + 64 half-rate vector
-      // instructions (~1 400 cycles) and 64 MFMAs (~1 300) per chunk and wave, whatever their order.  Same products, same order of accumulation, same
-      // dropout words: bit-identical to the plain loop (tests/test_fused256_gpu.py::test_pipelined_ffn_loop_is_bit_identical).
-      auto gbuf = [&](int c) -> LT* { return (c & 1) ? Actx : Ag; };
-      // one (feature tile ect, row tile ert) piece of the epilogue of chunk ch: dropout before the GELU (quirk Q4), GELU, store to the g tile
-      float kq[2][4];                                     // dropout multipliers of row tile ert: [0] feature tile 0, [1] feature tile 1
-      auto epi_piece = [&](f32x4 (&h)[2][RT], int ch, LT* gdst, int ert, int ect) {
-        if constexpr (DM != 0) {
-          if (ect == 0) {
-            const unsigned int rb = (unsigned int)(mb[ert] + li) * (unsigned int)a.dff + (unsigned int)(ch * FD + n0 + 4 * lg);
-            if constexpr (DM == 1) {
-              const unsigned int w = rg_hash(drop1.seed, rb >> 5);
-              load4f(kq[0], reinterpret_cast<const float*>(reinterpret_cast<const char*>(klut) + (__builtin_amdgcn_alignbit(w, w, rot0) & 0xF0u)));
-              load4f(kq[1], reinterpret_cast<const float*>(reinterpret_cast<const char*>(klut) + (__builtin_amdgcn_alignbit(w, w, rot1) & 0xF0u)));
-            } else {
-              rg_keep4_pair(drop1, rb, kq[0], kq[1]);
-            }
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) h[ect][ert][r] *= kq[ect][r];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r += 2) {
-          const f32x2 gg = gelu2_fast((f32x2){h[ect][ert][r], h[ect][ert][r + 1]});
-          h[ect][ert][r] = gg.x;
-          h[ect][ert][r + 1] = gg.y;
-        }
-        float t[4] = {h[ect][ert][0], h[ect][ert][1], h[ect][ert][2], h[ect][ert][3]};
-        store4(gdst + Tile<LT>::off(ert * 16 + li, n0 + ect * 16 + 4 * lg), t);
-      };
-      // ---- chunk 0 (wp = W1 chunk 0, prefetched behind LayerNorm 1): nothing to run beside its epilogue yet
-      init_acc(acc, p_b1, n0, lg);
-      mma_wset<T>(acc, wp, Ay, li, lg);
-      load_wset(wp, W1 + (unsigned int)(FD * FD), FD, n0, 0, li, lg, a.w_packed);
-      load_wset(wq, W2, a.dff, n0, 0, li, lg, a.w_packed);
-#pragma unroll
-      for (int u = 0; u < 2 * RT; ++u) epi_piece(acc, 0, gbuf(0), u >> 1, u & 1);
-      lds_barrier();
-#pragma unroll 1
-      for (int ch = 1; ch < nchunk; ++ch) {
-        init_acc(acc, p_b1 + ch * FD, n0, lg);
-        mma_wset<T>(acc, wp, Ay, li, lg);                                    // h1 of chunk ch
-        load_wset(wp, (ch + 1 < nchunk) ? W1 + (unsigned int)(ch + 1) * (FD * FD) : Wo, FD, n0, 0, li, lg, a.w_packed);
-        __builtin_amdgcn_sched_barrier(0);
-        // out += g(ch - 1) . W2[:, chunk ch - 1]^T in eight slices of 4 MFMAs (k-step u >> 1, row tiles 2 (u & 1), + 1), each followed
-        // by one piece of the epilogue of chunk ch; nothing crosses a slice boundary, so every group of 4 matrix instructions runs
-        // under ~30 VALU instructions of the same wave (the fragments of the next slice are read a slice ahead)
-        const LT* gprev = gbuf(ch - 1);
-        LT* gcur = gbuf(ch);
-        typename OpT<T>::type af[2][2];
-        load_frag(af[0][0], gprev + Tile<LT>::off(li, 8 * lg));
-        load_frag(af[0][1], gprev + Tile<LT>::off(16 + li, 8 * lg));
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int ks = u >> 1, rh = (u & 1) * 2;
-          if (u < 7) {
-            const int ksn = (u + 1) >> 1, rhn = ((u + 1) & 1) * 2;
-            load_frag(af[(u + 1) & 1][0], gprev + Tile<LT>::off(rhn * 16 + li, ksn * 32 + 8 * lg));
-            load_frag(af[(u + 1) & 1][1], gprev + Tile<LT>::off((rhn + 1) * 16 + li, ksn * 32 + 8 * lg));
-          }
-          // ONE matrix instruction, then half a GELU pair (>= 40 cycles of VALU / transcendental work against the 16 the matrix pipe
-          // is busy): a wave issues in order, so matrix instructions back to back would stall it on the pipe before its first VALU one
-          const int ert = u >> 1, ect = u & 1;
-          if constexpr (DM != 0) {
-            if (ect == 0) {
-              const unsigned int rb = (unsigned int)(mb[ert] + li) * (unsigned int)a.dff + (unsigned int)(ch * FD + n0 + 4 * lg);
-              if constexpr (DM == 1) {
-                const unsigned int w = rg_hash(drop1.seed, rb >> 5);
-                load4f(kq[0], reinterpret_cast<const float*>(reinterpret_cast<const char*>(klut) + (__builtin_amdgcn_alignbit(w, w, rot0) & 0xF0u)));
-                load4f(kq[1], reinterpret_cast<const float*>(reinterpret_cast<const char*>(klut) + (__builtin_amdgcn_alignbit(w, w, rot1) & 0xF0u)));
-              } else {
-                rg_keep4_pair(drop1, rb, kq[0], kq[1]);
-              }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[ect][ert][r] *= kq[ect][r];
-          }
-          f32x2 xa = (f32x2){acc[ect][ert][0], acc[ect][ert][1]}, xb = (f32x2){acc[ect][ert][2], acc[ect][ert][3]};
-          __builtin_amdgcn_sched_barrier(0);
-          mma(wq.f[ks][0], af[u & 1][0], acc2[0][rh]);
-          __builtin_amdgcn_sched_barrier(0);
-          const f32x2 ea = gelu2_fast_a(xa);
-          __builtin_amdgcn_sched_barrier(0);
-          mma(wq.f[ks][1], af[u & 1][0], acc2[1][rh]);
-          __builtin_amdgcn_sched_barrier(0);
-          xa = gelu2_fast_b(xa, ea);
-          __builtin_amdgcn_sched_barrier(0);
-          mma(wq.f[ks][0], af[u & 1][1], acc2[0][rh + 1]);
-          __builtin_amdgcn_sched_barrier(0);
-          const f32x2 eb = gelu2_fast_a(xb);
-          __builtin_amdgcn_sched_barrier(0);
-          mma(wq.f[ks][1], af[u & 1][1], acc2[1][rh + 1]);
-          __builtin_amdgcn_sched_barrier(0);
-          xb = gelu2_fast_b(xb, eb);
-          float t[4] = {xa.x, xa.y, xb.x, xb.y};
-          store4(gcur + Tile<LT>::off(ert * 16 + li, n0 + ect * 16 + 4 * lg), t);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        load_wset(wq, W2, a.dff, n0, ch * FD, li, lg, a.w_packed);
-        lds_barrier();                                                       // g(ch) visible; every reader of g(ch - 1) is done
-      }
-      mma_wset<T>(acc2, wq, gbuf(nchunk - 1), li, lg);
-    } else {
 #pragma unroll 1
     for (int ch = 0; ch < nchunk; ++ch) {
       load_wset(wq, W2, a.dff, n0, ch * FD, li, lg, a.w_packed);    // needed after the GELU below
@@ -713,9 +585,7 @@ void post_attn_fwd_kernel(rg_post_attn_args a) {
       // pointer (loads under a branch made hipcc drain vmcnt(0) at the join: the W2 fragments just issued above, i.e.
       // one exposed L2 latency per chunk; Wo is fetched needlessly after a workgroup's last tile, 32 KB once)
       load_wset(wp, (ch + 1 < nchunk) ? W1 + (unsigned int)(ch + 1) * (FD * FD) : Wo, FD, n0, 0, li, lg, a.w_packed);
-      STAMP(4);
       if (ch > 0) lds_barrier();                        // previous chunk's readers of Ag / Ah are done
-      STAMP(5);
       if constexpr (DM != 0) {  // dropout BEFORE the GELU (transformer.py:182-184, quirk Q4)
         // p == 0.5, four row tiles: the hash word of row tile rt is the same in the four lane rows lg -- lane row lg computes the word of
         // row tile lg only and the four are exchanged (rg_allgather_rows): one hash per lane and chunk instead of four
@@ -757,13 +627,9 @@ void post_attn_fwd_kernel(rg_post_attn_args a) {
           }
         }
       regs_to_tile<LT>(acc, Ag, n0, li, lg);
-      STAMP(6);
       lds_barrier();
-      STAMP(7);
       if (h1save) tile_to_hbm<T, true>(Ah, h1save, a.dff, ch * FD, mb, a.M, tid);
       mma_wset<T>(acc2, wq, Ag, li, lg);                // out += g . W2[:, chunk]^T
-      STAMP(8);
-    }
     }
     // prefetch the next tile's ctx / x rows while the second LayerNorm runs (unconditional: see next_group)
     prefetch_rows(mbn);
@@ -812,12 +678,10 @@ void post_attn_fwd_kernel(rg_post_attn_args a) {
         for (int r = 0; r < 4; ++r) acc2[ct][rt][r] *= rm4[rt];
     regs_to_tile<XT>(acc2, Aout, n0, li, lg);
     if constexpr (RES) regs_to_tile_lo<LT>(acc2, Ag, n0, li, lg);  // (the barrier inside ln_regs: the last g chunk has been consumed)
-    STAMP(9);
     lds_barrier();
     tile_to_hbm<T>(Aout, out, FD, 0, mb, a.M, tid);
     if constexpr (RES) tile_to_hbm<T>(Ag, outlo, FD, 0, mb, a.M, tid);
     lds_barrier();                                      // before the next tile overwrites Actx / Ag / Ay
-    STAMP(10);
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) mb[rt] = mbn[rt];
     have = have_next;
@@ -848,12 +712,6 @@ void post_attn_fwd_kernel(rg_post_attn_args a) {
       }
     }
   }
-#ifdef RG_STAMP
-  if (a.rstd_c == nullptr && a.o_bcast == nullptr && a.y2_save != nullptr && (tid & 63) == 0) {
-    unsigned long long* dbg = reinterpret_cast<unsigned long long*>(a.y2_save) + (size_t)(blockIdx.x * 4 + wave) * 12;
-    for (int i = 0; i < 12; ++i) dbg[i] = tacc[i];
-  }
-#endif
 }
 
 // bytes of one [rows x 128] activation tile in LDS: bf16 swizzled rows; f32 padded rows; bf16x3 a hi and a lo bf16 tile
@@ -862,15 +720,10 @@ static int act_tile_bytes(int dtype, int rows) {
 }
 
 int rg_post_attn_fwd256(const rg_post_attn_args* a, int dtype, hipStream_t s);      // fused256.hip: d_model == n_heads * 32 == 256
-int rg_post_attn_fwd_w8_try(const rg_post_attn_args* a, int dtype, hipStream_t s, int* rc);      // fused128w8.hip
 
 extern "C" int rg_post_attn_fwd(const rg_post_attn_args* a, int dtype, void* stream) {
   if (!a || a->M <= 0) return 0;
   if (a->d == 256) return rg_post_attn_fwd256(a, dtype, (hipStream_t)stream);
-  {
-    int rc8 = 0;                      // RG_PA8=1: the eight-wave prototype takes the encoder-inference launches (fused128w8.hip, A/B timing)
-    if (rg_post_attn_fwd_w8_try(a, dtype, (hipStream_t)stream, &rc8)) return rc8;
-  }
   if (a->d != FD || a->P != FD || (a->dff % FD) != 0 || a->dff <= 0)
     return rg_set_error_msg(RG_ERR_UNSUPPORTED, "post_attn_fwd: needs d_model == n_heads*32 == 128 and d_ff % 128 == 0");
   if ((long long)a->M * a->dff * (dtype == RG_BF16 ? 2 : 4) >= (1ll << 32))
@@ -881,17 +734,11 @@ extern "C" int rg_post_attn_fwd(const rg_post_attn_args* a, int dtype, void* str
   // work tile: 64 tokens.  The 32-token form (kernel template RT = 2: three workgroups per CU instead of two) was built and
   // measured SLOWER at the bench shape -- 277 -> 292 us (encoder inference), 337 -> 365, 413 -> 467 (decoder training): the
   // per-tile fixed costs (14 barriers, two LayerNorm exchanges, the weight sets) double per row, which the third wave per
-  // SIMD does not buy back.  It is only instantiated in -DRG_PA_RT2 builds (RG_PA_RT=2 selects it there) for A/B timing.
+  // SIMD does not buy back (was measured, removed: DESIGN.md 6a).
   // bf16x3: the 64-token form holds 96 KB of split tiles -- ONE workgroup per CU, one wave per SIMD, nothing to overlap the
-  // MFMA, VALU and LDS phases of a tile with; the 32-token form (48 KB) puts two workgroups on a CU (RG_X3_PA_RT=4: the 64-token
-  // form, for A/B timing)
-  static const int x3_rt = [] { const char* e = getenv("RG_X3_PA_RT"); return (e && atoi(e) == 4) ? 4 : 2; }();
-#ifdef RG_PA_RT2
-  static const int rt_env = [] { const char* e = getenv("RG_PA_RT"); return e ? atoi(e) : 0; }();
-  const int rt = dtype == RG_X3 ? x3_rt : (dtype != RG_BF16 ? 4 : (rt_env == 2 ? 2 : 4));
-#else
-  const int rt = dtype == RG_X3 ? x3_rt : 4;
-#endif
+  // MFMA, VALU and LDS phases of a tile with; the 32-token form (48 KB) puts two workgroups on a CU (the 64-token bf16x3 form
+  // was measured, removed: DESIGN.md 6a)
+  const int rt = dtype == RG_X3 ? 2 : 4;
   const int ftm = 16 * rt;
   const int ntiles = (a->M + ftm - 1) / ftm;
   const int act = act_tile_bytes(dtype, ftm);
@@ -906,40 +753,12 @@ extern "C" int rg_post_attn_fwd(const rg_post_attn_args* a, int dtype, void* str
   const bool res = a->x_lo || a->out_lo;
   if (res && (!a->x_lo || !a->out_lo || dtype != RG_BF16))
     return rg_set_error_msg(RG_ERR_INVALID, "post_attn_fwd: the split residual stream needs x_lo AND out_lo, bf16 tier");
-  // RG_PA_PIPE=1: the software-pipelined FFN loop (bf16 inference launches: no saves, no cross stage, one residual stream, d_ff >= 256) --
-  // bit-identical, measured 0 ... 3 % SLOWER than the plain loop, kept for A/B timing
-  static const int pipe_on = [] { const char* e = getenv("RG_PA_PIPE"); return e ? atoi(e) : 0; }();
-  if (pipe_on && dtype == RG_BF16 && !cross && !save && !res && a->dff >= 2 * FD) {
-#define RG_PAP(DM)                                                                                                        \
-  do {                                                                                                                    \
-    hipFuncSetAttribute(reinterpret_cast<const void*>(post_attn_fwd_kernel<__bf16, DM, false, false, false, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem); \
-    hipLaunchKernelGGL((post_attn_fwd_kernel<__bf16, DM, false, false, false, 4, true>), dim3(grid), dim3(256), smem, s, *a); \
-  } while (0)
-    if (dm == 0) RG_PAP(0);
-    else if (dm == 1) RG_PAP(1);
-    else RG_PAP(2);
-#undef RG_PAP
-    RG_CHECK_LAUNCH();
-    return 0;
-  }
 #define RG_PA4(T, DM, C, S, R, RTV)                                                                                       \
   do {                                                                                                                    \
     hipFuncSetAttribute(reinterpret_cast<const void*>(post_attn_fwd_kernel<T, DM, C, S, R, RTV>), hipFuncAttributeMaxDynamicSharedMemorySize, smem); \
     hipLaunchKernelGGL((post_attn_fwd_kernel<T, DM, C, S, R, RTV>), dim3(grid), dim3(256), smem, s, *a);                  \
   } while (0)
-#ifdef RG_PA_RT2
-#define RG_PA3(T, DM, C, S, R)                                                              \
-  do {                                                                                      \
-    if constexpr (sizeof(T) == 2 || std::is_same<T, x3>::value) { if (rt == 2) RG_PA4(T, DM, C, S, R, 2); else RG_PA4(T, DM, C, S, R, 4); } \
-    else RG_PA4(T, DM, C, S, R, 4);                                                         \
-  } while (0)
-#else
-#define RG_PA3(T, DM, C, S, R)                                                              \
-  do {                                                                                      \
-    if constexpr (std::is_same<T, x3>::value) { if (rt == 2) RG_PA4(T, DM, C, S, R, 2); else RG_PA4(T, DM, C, S, R, 4); } \
-    else RG_PA4(T, DM, C, S, R, 4);                                                         \
-  } while (0)
-#endif
+#define RG_PA3(T, DM, C, S, R) RG_PA4(T, DM, C, S, R, (std::is_same<T, x3>::value ? 2 : 4))
 #define RG_PA2(T, DM, C, S)                                                                       \
   do {                                                                                            \
     if constexpr (sizeof(T) == 2) { if (res) RG_PA3(T, DM, C, S, true); else RG_PA3(T, DM, C, S, false); } \

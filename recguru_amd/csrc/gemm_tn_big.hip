@@ -538,24 +538,20 @@ __global__ __launch_bounds__(256) void tn_layer_reduce_kernel(rg_tn_layer_reduce
   else tn_reduce_body<128, 128>(m.p[3], m.grid1[3], m.ct[3], bx, by, m.gy[3]);
 }
 
-static int tn_use_dma() {            // RG_TN_REGSTAGE=1: the register-staged kernel (kept for A/B timing, tools/kb_tn.py)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("RG_TN_REGSTAGE"); v = (e && e[0] == '1') ? 0 : 1; }
-  return v;
-}
+// 192 workgroups, not one per CU: every workgroup leaves a partial dW tile (written, then read by the reduce launch), and
+// three quarters of the CUs already keep the memory system full (512x128 / 384x128 / 128x128 on the live rows of the bench
+// shape: 150.7 / 125.7 / 65.3 us at 256, 145.2 / 118.8 / 64.8 at 192, 145.7 / 117.1 / 67.8 at 160)
+static constexpr int TN_GRID_CAP = 192;
 
 template <int N1, int N2, typename T = __bf16>
 static int launch_big(const rg_gemm_tn_args& a, hipStream_t s) {
   constexpr bool X3 = std::is_same<T, x3>::value;           // bf16x3: the register-staged kernel (its rows are split on the way to LDS)
-  // the DMA kernel keeps its slice of the live-tile list in LDS behind the ring: T up to ~4 M rows (64 K chunks per workgroup)
-  const bool dma = !X3 && tn_use_dma() != 0 && (long long)TnDma<N1, N2>::NST * TnDma<N1, N2>::STG + ((a.T + 31) / 32 / 256 + 2) * 8 <= 160 * 1024;
+  // the DMA kernel keeps its slice of the live-tile list in LDS behind the ring: T up to ~4 M rows (64 K chunks per workgroup); beyond
+  // that the register-staged kernel (bf16 below that size: was measured, removed as a switch -- DESIGN.md 6a)
+  const bool dma = !X3 && (long long)TnDma<N1, N2>::NST * TnDma<N1, N2>::STG + ((a.T + 31) / 32 / 256 + 2) * 8 <= 160 * 1024;
   const int ct = dma ? TnDma<N1, N2>::CT : (X3 ? TB_T_X3 : TB_T_BF16);
   const int nchunks = (a.T + ct - 1) / ct;
-  // 192 workgroups, not one per CU: every workgroup leaves a partial dW tile (written, then read by the reduce launch), and
-  // three quarters of the CUs already keep the memory system full (512x128 / 384x128 / 128x128 on the live rows of the bench
-  // shape: 150.7 / 125.7 / 65.3 us at 256, 145.2 / 118.8 / 64.8 at 192, 145.7 / 117.1 / 67.8 at 160).  RG_TN_GRID overrides.
-  static const int grid_cap = [] { const char* e = getenv("RG_TN_GRID"); const int v = e ? atoi(e) : 0; return v > 0 && v <= 256 ? v : 192; }();
-  int grid = nchunks < grid_cap ? nchunks : grid_cap;
+  int grid = nchunks < TN_GRID_CAP ? nchunks : TN_GRID_CAP;
   const int per = (nchunks + grid - 1) / grid;
   const int smem = dma ? TnDma<N1, N2>::NST * TnDma<N1, N2>::STG + (TnDma<N1, N2>::CT / 16) * per * 4
                        : (X3 ? TB_T_X3 * (N1 + 8 + N2 + 8) * 2 * 2 : TB_T_BF16 * (N1 + 8 + N2 + 8) * 2);
@@ -610,7 +606,7 @@ int rg_gemm_tn_big_select(const rg_gemm_tn_args* a, int dtype) {
 // kernel family that runs the big shapes (profiler names: rg_gemm_tn_plan)
 const char* rg_gemm_tn_big_name(const rg_gemm_tn_args* a) {
   const bool fits = (long long)3 * 40 * 1024 + ((a->T + 31) / 32 / 256 + 2) * 8 <= 160 * 1024;
-  return tn_use_dma() && fits ? "gemm_tn_dma_kernel" : "gemm_tn_big_kernel";
+  return fits ? "gemm_tn_dma_kernel" : "gemm_tn_big_kernel";
 }
 
 // bytes of partial-sum scratch the big kernel can use for this problem (0 if it does not take it)
@@ -680,7 +676,7 @@ static int layer_lds(const rg_gemm_tn_args& a, int i, int g, int dtype) {
 }
 
 extern "C" int rg_gemm_tn_layer_supported(const rg_gemm_tn_args* p, const int* wgs, int dtype) {
-  if (!p || !wgs || (dtype != RG_BF16 && dtype != RG_X3) || (dtype == RG_BF16 && !tn_use_dma())) return 0;
+  if (!p || !wgs || (dtype != RG_BF16 && dtype != RG_X3)) return 0;
   int tot = 0;
   for (int i = 0; i < 4; ++i) {
     const rg_gemm_tn_args& a = p[i];

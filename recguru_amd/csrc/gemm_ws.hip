@@ -20,14 +20,14 @@
 #define WS_LD (128 + 8)
 #define WS_PLANE (WS_M * WS_LD * 2)      // bf16x3: bytes between the hi and the lo image of the A tile
 #include <type_traits>
-#include <cstdlib>
 #include "rg_common.hip.h"
 #include "../../include/recguru_hip.h"
 
 // AUX: the epilogue reads an aux operand (compile-time: a load under a runtime condition gets a vmcnt(0) at the join,
 // which also drained the next tile's A prefetch -- one exposed HBM latency per tile even for the aux-free GEMMs)
 // WP (bf16x3, K > 128): 0 the weight slice is f32 and split in the kernel; 1 it is the PRESPLIT fragment-packed copy (rg_gemm_nt_args.w_packed),
-// streamed per tile and chunk like the f32 one; 2 (K = 256, no aux operand) presplit AND stationary -- 16 fragments = 128 VGPRs, affordable
+// streamed per tile and chunk like the f32 one (the aux epilogues; without an aux operand this form was measured, removed -- DESIGN.md 6a);
+// 2 (K = 256, no aux operand) presplit AND stationary -- 16 fragments = 128 VGPRs, affordable
 // once the in-kernel split's temporaries are gone and the activation fragments are read one k-step at a time
 template <typename T, int NKC, int NCB, bool AUX, int WP = 0>
 __global__ __launch_bounds__(256, 2) void gemm_ws_kernel(rg_gemm_nt_args a) {
@@ -250,12 +250,7 @@ __global__ __launch_bounds__(256, 2) void gemm_ws_kernel(rg_gemm_nt_args a) {
                 if (a.epilogue == RG_EPI_NONE) {
                   Frag<T> raw;
                   unstage8(raw, Cs + r * WS_LD + c8);
-#ifdef RG_ABL_WS_NT      // timing experiment (tools/ab_round6.sh x3nt): the plain-epilogue output rows of the f32-storage tiers by nontemporal stores
-                  if constexpr (sizeof(T) == 4) frag_store_nt(C + off, raw);
-                  else *reinterpret_cast<Frag<T>*>(C + off) = raw;
-#else
-                  *reinterpret_cast<Frag<T>*>(C + off) = raw;
-#endif
+                  *reinterpret_cast<Frag<T>*>(C + off) = raw;      // (nontemporal stores of the f32-storage tiers' rows: was measured, removed -- DESIGN.md 6a)
                 } else if (a.epilogue == RG_EPI_DROP_GELU) {
                   // h1 = dropout(l1) as the backward reads it back, and the activated operand of the second product, from
                   // the value AS STORED (rounded to T): what rg_dropout_gelu does in a pass of its own
@@ -350,18 +345,14 @@ static int launch_ws(const rg_gemm_nt_args& a, hipStream_t s, int ny = 1) {
   // would run with half the CUs idle).  bf16: 35 KB of LDS, <= 128 VGPRs -- up to four per CU (768 measured best); bf16x3: two A
   // planes + an f32 C tile = 70 KB -- two per CU, 512 slots
   const int slots = std::is_same<T, x3>::value ? 512 : 768;
-  static const int slots_env = getenv("RG_WS_SLOTS") ? atoi(getenv("RG_WS_SLOTS")) : 0;
-  int grid = ny > 1 ? ((slots_env ? slots_env : slots) / ny > 96 ? (slots_env ? slots_env : slots) / ny : 96) : 512;
+  int grid = ny > 1 ? (slots / ny > 96 ? slots / ny : 96) : 512;
   if (grid > ntiles) grid = ntiles;
-  static const int no_xcd = getenv("RG_WS_NO_XCD") ? atoi(getenv("RG_WS_NO_XCD")) : 0;
-  if (ny > 1 && grid >= 16) grid = (grid & ~7) - (no_xcd ? 1 : 0);     // walkers in multiples of 8: the XCD-aware block mapping (RG_WS_NO_XCD=1: one walker fewer = the plain mapping, for A/B)
+  if (ny > 1 && grid >= 16) grid &= ~7;      // walkers in multiples of 8: the XCD-aware block mapping (the plain mapping was measured, removed: DESIGN.md 6a)
   if constexpr (std::is_same<T, x3>::value && NKC == 2) {
     if (a.w_packed) {
-      static const int pstat = [] { const char* e = getenv("RG_WS_PSTAT"); return e ? atoi(e) : 1; }();   // RG_WS_PSTAT=0: stream the presplit slice per tile (A/B)
       const bool aux_epi = a.epilogue != RG_EPI_NONE && a.epilogue != RG_EPI_RELU && a.epilogue != RG_EPI_DROP_GELU;
       if (aux_epi) hipLaunchKernelGGL((gemm_ws_kernel<T, NKC, NCB, true, 1>), dim3(ny * grid), dim3(256), 0, s, a);
-      else if (pstat) hipLaunchKernelGGL((gemm_ws_kernel<T, NKC, NCB, false, 2>), dim3(ny * grid), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((gemm_ws_kernel<T, NKC, NCB, false, 1>), dim3(ny * grid), dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((gemm_ws_kernel<T, NKC, NCB, false, 2>), dim3(ny * grid), dim3(256), 0, s, a);
       RG_CHECK_LAUNCH();
       return 0;
     }

@@ -417,105 +417,11 @@ __global__ __launch_bounds__(64 * LW) void item_loss_train_rows_kernel(rg_item_l
 // The coefficients of the table gradient need the final lse, which is not known while the rows pass by: the kernel leaves
 // the RAW logits in cbuf and lse in aux_tok, and the binned scatter (bin_fill) forms c = (exp(l - lse) - [j == 0]) mask / count
 // from them while it sorts the pairs anyway.  The two-call form gathers the rows twice (0.47 TB each at config-5).
-template <typename T, int LPR>
-__global__ __launch_bounds__(64 * LW) void item_loss_train_online_kernel(rg_item_loss_args a, float* __restrict__ cbuf) {
-  constexpr int G = 64 / LPR;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int gi = lane / LPR, li = lane % LPR;
-  const T* __restrict__ H = reinterpret_cast<const T*>(a.h);
-  const T* __restrict__ E = reinterpret_cast<const T*>(a.table);
-  T* __restrict__ dH = reinterpret_cast<T*>(a.dh);
-  const int d = a.d, k = a.k, n = a.k + 1;
-  const float gs = 1.f / a.sums[1];
-  float lsum = 0.f;
-  for (long long t = (long long)blockIdx.x * LW + wave; t < a.ntok; t += (long long)gridDim.x * LW) {
-    const float m = a.mask[t];
-    float dh[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) dh[j] = 0.f;
-    if (m != 0.f) {
-      float h[8], e0[8], A[8];
-      load8(h, H + (size_t)t * d + 8 * li);
-      const long long pos = a.pos[t];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { A[j] = 0.f; e0[j] = 0.f; }
-      float mx = -INFINITY, sm = 0.f, l0 = 0.f;          // per row group
-      for (int i0 = 0; i0 < n; i0 += G * RG_U) {
-        long long item[RG_U];
-        float e[RG_U][8];
-#pragma unroll
-        for (int u = 0; u < RG_U; ++u) {
-          const int idx = i0 + u * G + gi;
-          item[u] = (idx == 0 || idx >= n) ? pos : a.neg[t * k + idx - 1];
-        }
-#pragma unroll
-        for (int u = 0; u < RG_U; ++u) load8(e[u], E + (size_t)item[u] * d + 8 * li);
-#pragma unroll
-        for (int u = 0; u < RG_U; ++u) {
-          const int idx = i0 + u * G + gi;
-          float dot = 0.f;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) dot += e[u][j] * h[j];
-          dot = group_sum<LPR>(dot);
-          if (idx < n) {
-            if (idx == 0) {
-              l0 = dot;
-#pragma unroll
-              for (int j = 0; j < 8; ++j) e0[j] = e[u][j];
-            }
-            if (li == 0) cbuf[t * n + idx] = dot;
-            const float nm = fmaxf(mx, dot);
-            const float r = __expf(mx - nm), p = __expf(dot - nm);     // (mx == -inf: r = 0, sm and A are still 0)
-            sm = sm * r + p;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) A[j] = A[j] * r + p * e[u][j];
-            mx = nm;
-          }
-        }
-      }
-      // combine the G row groups (a group that saw no row has mx = -inf and weight 0)
-      float M = mx;
-#pragma unroll
-      for (int o = LPR; o < 64; o <<= 1) M = fmaxf(M, __shfl_xor(M, o));
-      const float wg = mx == -INFINITY ? 0.f : __expf(mx - M);
-      sm *= wg;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) A[j] *= wg;
-#pragma unroll
-      for (int o = LPR; o < 64; o <<= 1) {
-        sm += __shfl_xor(sm, o);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) A[j] += __shfl_xor(A[j], o);
-      }
-      l0 = __shfl(l0, 0);
-      const float lse = M + __logf(sm);
-      lsum += (lse - l0) * m;
-      if (lane == 0) a.aux_tok[t] = lse;
-      const float w = m * gs, inv = 1.f / sm;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) dh[j] = (A[j] * inv - e0[j]) * w;       // e0 lives in group 0, which is the group that stores
-    } else if (lane == 0) {
-      a.aux_tok[t] = 0.f;
-    }
-    if (gi == 0) store8(dH + (size_t)t * d + 8 * li, dh);
-  }
-  __shared__ float red[LW];
-  if (lane == 0) red[wave] = lsum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s0 = 0.f;
-    for (int w = 0; w < LW; ++w) s0 += red[w];
-    if (s0 != 0.f) rg_acc(a.sums, s0);
-  }
-}
-
-
-// The same kernel with the gather PIPELINED (round 5): per 64 rows the item ids arrive by ONE coalesced load (lane l: row i0 + l; the next
-// 64 are requested a block ahead) and reach the lane groups through ds_bpermute -- the id load was a second dependent memory latency in
-// front of every batch of rows --, and the rows of batch s + 1 are requested BEFORE batch s is reduced (two register buffers), so a wave
-// keeps 2 x RG_U x G rows in flight instead of RG_U x G.  The rows of a lane group pass through the online recurrence in the same order:
-// bit-identical logits, lse, loss and dh (tests/test_kernels_gpu.py::test_item_loss_online_pipelined_equals_plain).  RG_ITEM_ONLINE_PLAIN=1
-// selects the plain kernel above (A/B).
+// The gather is PIPELINED (round 5): per 64 rows the item ids arrive by ONE coalesced load (lane l: row i0 + l; the next 64 are requested
+// a block ahead) and reach the lane groups through ds_bpermute -- the id load was a second dependent memory latency in front of every batch
+// of rows --, and the rows of batch s + 1 are requested BEFORE batch s is reduced (two register buffers), so a wave keeps 2 x RG_U x G rows
+// in flight instead of RG_U x G.  (The plain form -- ids loaded per batch, one buffer -- gave bit-identical logits, lse, loss and dh; was
+// measured, removed: DESIGN.md 6a.)
 template <typename T, int LPR>
 __global__ __launch_bounds__(64 * LW) void item_loss_train_online2_kernel(rg_item_loss_args a, float* __restrict__ cbuf) {
   constexpr int G = 64 / LPR, RS = G * RG_U, NS = 64 / RS;          // rows per step, steps per block of 64 rows (even)
@@ -1188,8 +1094,7 @@ static int launch_binned(const rg_item_loss_args& a, const float* coef, void* ws
   else if (a.d == 128) hipLaunchKernelGGL((item_loss_bwd_rows_kernel<T, 16, true>), dim3((int)g), dim3(64 * LW), 0, s, a, w.c);
   else hipLaunchKernelGGL((item_loss_bwd_rows_kernel<T, 32, true>), dim3((int)g), dim3(64 * LW), 0, s, a, w.c);
   // K2..K4
-  static const int ppw_wide_env = [] { const char* e = getenv("RG_PPW_WIDE"); return e ? atoi(e) : 0; }();      // (A/B: pairs per workgroup of count / fill)
-  w.ppw = w.nbins > 4096 ? (ppw_wide_env >= 8192 ? ppw_wide_env : RG_PPW_WIDE) : RG_PPW;
+  w.ppw = w.nbins > 4096 ? RG_PPW_WIDE : RG_PPW;
   const int gp = (int)((npairs + w.ppw - 1) / w.ppw);
   hipLaunchKernelGGL(bin_count_kernel, dim3(gp), dim3(256), (size_t)w.nbins * 4, s, a, w);
   hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, s, w);
@@ -1262,16 +1167,9 @@ static int launch_train(const rg_item_loss_args& a, float* coef, hipStream_t s) 
   if (!nit) {       // more rows than four register batches: the online form
     if (a.mode != RG_LOSS_SAMPLED_CE || !a.aux_tok)
       return rg_set_error_msg(RG_ERR_UNSUPPORTED, "item_loss_train: 1+k beyond 4 row batches takes the online form: sampled softmax only, aux_tok [ntok] required");
-    static const int plain = [] { const char* e = getenv("RG_ITEM_ONLINE_PLAIN"); return e ? atoi(e) : 0; }();
-    if (plain) {
-      if (a.d == 64) hipLaunchKernelGGL((item_loss_train_online_kernel<T, 8>), grid, block, 0, s, a, coef);
-      else if (a.d == 128) hipLaunchKernelGGL((item_loss_train_online_kernel<T, 16>), grid, block, 0, s, a, coef);
-      else hipLaunchKernelGGL((item_loss_train_online_kernel<T, 32>), grid, block, 0, s, a, coef);
-    } else {
-      if (a.d == 64) hipLaunchKernelGGL((item_loss_train_online2_kernel<T, 8>), grid, block, 0, s, a, coef);
-      else if (a.d == 128) hipLaunchKernelGGL((item_loss_train_online2_kernel<T, 16>), grid, block, 0, s, a, coef);
-      else hipLaunchKernelGGL((item_loss_train_online2_kernel<T, 32>), grid, block, 0, s, a, coef);
-    }
+    if (a.d == 64) hipLaunchKernelGGL((item_loss_train_online2_kernel<T, 8>), grid, block, 0, s, a, coef);
+    else if (a.d == 128) hipLaunchKernelGGL((item_loss_train_online2_kernel<T, 16>), grid, block, 0, s, a, coef);
+    else hipLaunchKernelGGL((item_loss_train_online2_kernel<T, 32>), grid, block, 0, s, a, coef);
     RG_CHECK_LAUNCH();
     return 0;
   }

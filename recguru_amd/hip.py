@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # more than one wave can reach is an integer atomic on a 64-bit fixed-point shadow -- any summation order gives the same bits).
 # The wrappers below that hand a kernel an accumulator are marked @_det_accum / use _DetScope; in the default mode those are no-ops.
 DETERMINISTIC = os.environ.get("RG_DETERMINISTIC", "0") not in ("", "0")
-LIB_PATH = os.environ.get("RG_HIP_LIB") or os.path.join(_HERE, "librecguru_hip_det.so" if DETERMINISTIC else "librecguru_hip.so")   # RG_HIP_LIB: another build of the SAME library (A/B kernel experiments, tools/ab_variants.sh)
+LIB_PATH = os.environ.get("RG_HIP_LIB") or os.path.join(_HERE, "librecguru_hip_det.so" if DETERMINISTIC else "librecguru_hip.so")   # RG_HIP_LIB: another build of the SAME library
 _lib = None
 
 F32, BF16, X3 = 0, 1, 2
@@ -432,13 +432,12 @@ def _gemm_tn(Y, X, dW, colsum, prologue_x, scale, splits, use_tr, live, partials
 
 
 LAYER_SLOTS = ((128, 512, PRO_GELU), (512, 128, PRO_NONE), (384, 128, PRO_NONE), (128, 128, PRO_NONE))      # (N1, N2, prologue) of rg_gemm_tn_layer
-LAYER_WGS = int(os.environ.get("RG_TN_LAYER_WGS", "256"))     # workgroups of the merged launch (one per CU: ~159 KB of LDS each)
+LAYER_WGS = 256     # workgroups of the merged launch (one per CU: ~159 KB of LDS each)
 # relative cost per streamed byte of the four slots (the workgroups of the one launch are dealt in proportion to bytes x cost): slot 0
 # evaluates GELU on its 512-wide operand rows while it stages them
 # (measured, bench shape, profiles/r05/ab/tn_layer_cost_sweep.txt: equal weights 7.58 ms per step, 1.3 -> 6.52, 1.5 -> 6.41, 1.7 -> 6.53, 2.0 -> 6.63)
-_LC = os.environ.get("RG_TN_LAYER_COST")
-LAYER_COST = {False: tuple(float(x) for x in (_LC or "1.45,1,1,1").split(",")),           # bf16 tier (LDS-DMA bodies)
-              True: tuple(float(x) for x in (_LC or os.environ.get("RG_TN_LAYER_COST_X3", "1,1,1,1")).split(","))}   # bf16x3 (register-staged bodies)
+LAYER_COST = {False: (1.45, 1.0, 1.0, 1.0),           # bf16 tier (LDS-DMA bodies)
+              True: (1.0, 1.0, 1.0, 1.0)}              # bf16x3 (register-staged bodies)
 
 
 class _TnLayerArgs(ctypes.Structure):
@@ -1223,8 +1222,8 @@ def attn_lastq_x_bwd(x, q_last, dctx, wk, wv, bk, bv, key_ids, pad_value, dbv, d
     return dx, dq, ops4[0], ops4[1], ops4[2], ops4[3]
 
 
-PRESPLIT_WS_X3 = not os.environ.get("RG_NO_PRESPLIT_WS")     # RG_NO_PRESPLIT_WS=1: the bf16x3 weight-stationary products at K > 128 split their weight slices in the kernel (A/B timing)
-FUSE_BLOCK_256 = not os.environ.get("RG_NO_PA256")      # RG_NO_PA256=1: d_model 256 takes the unfused launches (A/B timing)
+PRESPLIT_WS_X3 = True     # False: the bf16x3 weight-stationary products at K > 128 split their weight slices in the kernel
+FUSE_BLOCK_256 = True      # False: d_model 256 takes the unfused launches (the reference side of a test)
 
 
 def post_attn_supported(d, P, dff, dtype=None, M=None):

@@ -7,6 +7,7 @@ set_compute_dtype(): torch.bfloat16 (bf16 MFMA, default) or torch.float32 (exact
 parity tier).  Tier copies ("shadows") of the weights, plain and transposed, are cached per
 parameter version so they are rebuilt only after an optimizer step.
 """
+import os
 import weakref
 
 import torch
@@ -272,11 +273,6 @@ def _head_eye(H, like):
     return e
 
 
-def _os_env(name):
-    import os
-    return os.environ.get(name)
-
-
 def _z(n, like):
     return torch.zeros(n, device=like.device, dtype=torch.float32)
 
@@ -321,13 +317,12 @@ def _live_tn(rowmask, M, n1, n2):
 
 
 TN_LIST_WIDE = True
-LISTS_256 = not _os_env("RG_NO_LISTS_256")      # d_model 256: list-driven unfused backward (RG_NO_LISTS_256=1: every row, A/B)
+LISTS_256 = True      # d_model 256: list-driven unfused backward (False: every row)
 
 # The weight-gradient products of a layer's backward are collected and issued as ONE launch (rg_gemm_tn_layer: the four products
 # of a d_model = 128 transformer layer) when the layer function opens a _tn_layer() context; products that do not fit a slot, and
 # everything outside such a context, go out one by one as before.
-import os as _os1
-TN_PER_LAYER = not _os1.environ.get("RG_NO_TN_LAYER")      # RG_NO_TN_LAYER=1: one launch per product (A/B timing)
+TN_PER_LAYER = True      # False: one launch per product
 import threading as _threading
 # The open batch belongs to the THREAD that opened it (autograd runs backward nodes on per-device worker threads; a re-entrant or
 # concurrent backward must not append to another layer's batch -- ADVICE r4).  The deferred products keep their operands
@@ -495,8 +490,7 @@ FUSE_QKV_INFERENCE = False  # True: no-grad layer passes project Q / K / V insid
                             # form).  Correct (tests) but SLOWER at the bench shape: 467 us against 254 + 122 us -- the per-head
                             # projection needs 252 row-strided fragment loads per workgroup and the vector L1 / TA becomes the
                             # bound at four workgroups per CU
-import os as _os
-_DEBUG = bool(_os.environ.get("RG_DEBUG"))
+_DEBUG = bool(os.environ.get("RG_DEBUG"))
 _X_MASKED = False      # set by masked_input(): the layer functions' input rows are zero wherever their row mask is
 
 
@@ -624,7 +618,7 @@ def _ws_tier():
     return _COMPUTE == torch.bfloat16 or (hip.SPLIT_OPERANDS and WS_WIDE_X3)
 
 
-WS_WIDE_X3 = not _os_env("RG_NO_WS_WIDE_X3")      # RG_NO_WS_WIDE_X3=1: the bf16x3 tier keeps the generic LayerNorm-epilogue products at d_model 256 (A/B)
+WS_WIDE_X3 = True      # False: the bf16x3 tier keeps the generic LayerNorm-epilogue products at d_model 256 (the reference side of a test)
 
 
 def _fusable(x2, Wo, W1):
@@ -652,13 +646,12 @@ def _lo_out(sv, shape):
 
 
 QKV_BIAS_ROWS_IN_ATTENTION = True
-import os as _os0
-QKV_HEAD_MAJOR = not _os0.environ.get("RG_NO_HM")        # head-major q | k | v + LDS-DMA staging in the attention forward
-QKV_HEAD_MAJOR_TRAIN = not _os0.environ.get("RG_NO_HM_TRAIN")   # ... in training passes too (the backward reads head-major qkv)
+QKV_HEAD_MAJOR = True          # head-major q | k | v + LDS-DMA staging in the attention forward
+QKV_HEAD_MAJOR_TRAIN = True    # ... in training passes too (the backward reads head-major qkv)
 EMBED_SCATTER_BINNED = True  # rg_embed_scatter_bwd_binned at >= 65536 positions
 FUSE_ITEM_LOSS_TRAIN = True   # rg_item_loss_train: loss, coefficients and dh from one gather of the 1+k rows
 FUSE_ATTN_OUT_BWD = True     # rg_attn_out_bwd (LayerNorm-1 backward + dctx product) for d_model == P == 128
-LASTQ_FROM_X = not _os_env("RG_NO_LASTQ_X")   # rg_attn_lastq_x_* / _xf_*: the last layer's single-query attention straight from x (no K / V); RG_NO_LASTQ_X=1: A/B
+LASTQ_FROM_X = True   # rg_attn_lastq_x_* / _xf_*: the last layer's single-query attention straight from x (no K / V)
 LASTQ_FOLD_PREFIX = True
 
 

@@ -83,19 +83,19 @@ def rowmajor_index(row, col, ncols):
     """row * ncols + col for a [rows, ncols] activation, in 32 bits.  The sites that use it:
       dropout_ / dropout_gelu / add_drop_ln / ln_bwd dz_drop   elementwise.hip:1016, 1024 (flat i == m*N + c), 1041, 1074, 410
       gemm_nt EPI_RELU + drop_p (generic kernel, tail)        gemm.hip:189, 223
-      gemm_nt EPI_DROP_GELU (weight-stationary kernel)         gemm_ws.hip:266
+      gemm_nt EPI_DROP_GELU (weight-stationary kernel)         gemm_ws.hip:261
       embedding gather / scatter (row = token b*L + t)         elementwise.hip:42, 117, 191, 229, 304
       fused FFN block: h1 (ncols = d_ff, seed_h1), out (ncols = d, seed_out)
-                                                               fused.hip:613, 726, 775; fused256.hip:283; fused128w8.hip:201
-      ffn_bwd_data's LayerNorm backward (ln=...)              fused.hip:1121
+                                                               fused.hip:596, 641; fused256.hip:283
+      ffn_bwd_data's LayerNorm backward (ln=...)              fused.hip:940
       discriminator layer i (row0 + t, ncols = n_i)            disc.hip:94"""
     return _wrap(np.asarray(row, dtype=np.uint64) * np.uint64(ncols) + np.asarray(col, dtype=np.uint64))
 
 
 def attn_index(b, h, q, key, H, L):
     """((b*H + h)*L + q) * LPAD + key, LPAD = lpad(L), in 32 bits: the attention map (rg_common.hip.h rg_lpad comment).
-    Sites: attention.hip:145-162 (fill_dmask, p == 0.5 forward / bf16 backward), 736-742 (forward, 16-bit mode), 930 / 1002
-    (f32 backward), 1098-1099, 1353, 1481 (bf16 / bf16x3 backward); the single-query kernels use row q = L-1 of the same
+    Sites: attention.hip:138-155 (fill_dmask, p == 0.5 forward / bf16 backward), 721-727 (forward, 16-bit mode), 902 / 974
+    (f32 backward), 1070-1071, 1325, 1451 (bf16 / bf16x3 backward); the single-query kernels use row q = L-1 of the same
     space (attention_lastq.hip:100, 140; attention_lastq_x.hip:294, 426, 671, 763); cross_drop_scale the same space for the
     uniform cross-attention map (elementwise.hip:884-892)."""
     u = np.uint64

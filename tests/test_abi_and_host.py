@@ -87,6 +87,25 @@ def test_product_never_imports_oracle():
             assert "oracle" not in open(p).read(), fn
 
 
+def test_no_ab_switches_in_the_shipped_library():
+    """The launchers read ONE environment variable, the test hook RG_ATTN_BWD_TWO_PHASE (read on every launch), and hip.py / ops.py read
+    only the names that configure a run -- no A/B switch that a stray variable in a shell could flip (DESIGN.md 6a keeps the findings)."""
+    csrc = os.path.join(ROOT, "recguru_amd", "csrc")
+    reads = []
+    for fn in sorted(os.listdir(csrc)):
+        src = open(os.path.join(csrc, fn)).read()
+        reads += [(fn, m.group(1)) for m in re.finditer(r"getenv\(\s*([^)]*)\)", src)]
+    assert reads == [("attention.hip", '"RG_ATTN_BWD_TWO_PHASE"')], reads
+    kept = {"RG_DETERMINISTIC", "RG_HIP_LIB", "RG_ALLOW_UNSCREENED", "RG_DET_ARENA_MFLOATS", "RG_DEBUG"}
+    for fn in ("hip.py", "ops.py"):
+        src = open(os.path.join(ROOT, "recguru_amd", fn)).read()
+        names = re.findall(r"os\.environ\.get\(\"([A-Za-z0-9_]+)\"", src)
+        assert len(names) == len(re.findall(r"environ|getenv", src)), "%s reads the environment in a form this test cannot name" % fn
+        extra = [n for n in names if n not in kept and not n.startswith(("RG_DP_", "RG_BENCH_"))]
+        assert not extra, (fn, extra)
+        assert not re.search(r"import os as ", src), fn
+
+
 def test_get_param_surface_matches_reference_defaults(tmp_path):
     """Attribute values of the reference get_param for its own defaults (config_auto4rec.py)."""
     from recguru_amd.config import get_param

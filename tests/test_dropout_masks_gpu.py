@@ -409,6 +409,39 @@ def test_attention_masks(tier, L, p, seed):
             torch.testing.assert_close(dkv.double(), x.grad[:, :, P:], **t)
 
 
+@pytest.mark.parametrize("tier,L", [("bf16", 260), ("bf16", 416),                          # the 26-tile eight-wave form
+                                    ("x3", 130), ("x3", 224), ("x3", 230), ("x3", 416)])   # restaged <14>, <14>, <16>, <26>
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("p", [0.0, 0.5])
+def test_attention_backward_long_forms(tier, L, causal, p):
+    """The backward forms the launcher selects by length alone, at the lower and the upper edge of their ranges, B = 2, H = 4, causal and
+    not, without dropout and at p = 0.5: ctx and dqkv against float64 autograd through softmax(...) * host mask -- reference and tolerances
+    of test_attention_masks."""
+    from recguru_amd import hip
+    dt = _tier(tier)
+    B, H, seed = 2, 4, SEEDS[0]
+    P = H * 32
+    pad = 0 if causal else 51
+    ids, rm = _attn_case(B, L, H, L)
+    qkv = _rnd(B, L, 3 * P, seed=L + 1, dt=dt)
+    km = _dev(dm.attn_mask(seed, p, H, L, range(B))) if p > 0 else torch.ones(B, H, L, L, dtype=torch.float64, device="cuda")
+    dctx = (_rnd(B, L, P, seed=L + 3, dt=dt) * rm.view(B, L, 1).to(dt)).contiguous()
+    kw = dict(drop_p=p, seed=seed, rowmask=rm)
+    with _Tier(tier):
+        ctx, lse = hip.attn_fwd(qkv, ids, pad, causal, H, **kw)
+        dqkv = hip.attn_bwd(qkv, dctx, ctx, lse, ids, pad, causal, H, **kw)
+    x = qkv.double().requires_grad_(True)
+    cr, _, _, _ = _ref64(x, ids, pad, causal, H, km)
+    (cr * dctx.double()).sum().backward()
+    lv = rm.view(B, L) != 0
+    _close(ctx[lv], cr.detach()[lv], _tolkey(tier), "ctx")
+    if tier == "x3":
+        err = float((dqkv.double() - x.grad).abs().max()) / float(x.grad.abs().max())
+        assert err <= 6e-5, "dqkv: max error %.3g of max |value|" % err
+    else:
+        torch.testing.assert_close(dqkv.double(), x.grad, rtol=5e-2, atol=5e-2)
+
+
 # ================================================================================================================ past the wrap
 def test_attention_mask_past_the_32bit_wrap():
     """H = 8, L = 400 (LPAD 416), B = 3240: the attention index passes 2^32 inside sequence 3226 (head 3, query 40, key 256).

@@ -191,8 +191,9 @@ def test_post_attn256_bitwise_reproducible_and_chunk_invariant():
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32])
 @pytest.mark.parametrize("d,drop_p", [(128, 0.0), (128, 0.5), (256, 0.3)])
 def test_embed_row_form_equals_the_element_per_thread_kernel(dt, d, drop_p):
-    """rg_embed_pe_fwd2 (the row-form gather kernel, csrc/elementwise.hip, with its second bf16 output) against rg_embed_pe_fwd (the
-    default element-per-thread kernel): same bits in `out` -- same arithmetic, same dropout index space --, the second output is
+    """rg_embed_pe_fwd2 (the row-form gather kernel, csrc/elementwise.hip, with its second bf16 output) against rg_embed_pe_fwd (whole
+    sequences at d_model 128 / 256: the default position-major kernel; the name is from the time the element-per-thread kernel was the
+    default): same bits in `out` -- same arithmetic, same dropout index space --, the second output is
     `out` rounded to bf16; ragged token count, left-padded sequences (whole padded groups take the zero-fill path)."""
     from recguru_amd import hip
     B, L, V = 37, 50, 3000
@@ -210,133 +211,6 @@ def test_embed_row_form_equals_the_element_per_thread_kernel(dt, d, drop_p):
     assert bool((bits(out) == bits(ref)).all())
     assert out2.dtype == torch.bfloat16 and bool((bits(out2) == bits(ref.to(torch.bfloat16))).all())
     assert float(out[mask == 0].abs().max()) == 0.0
-
-
-_W8_WORKER = r'''
-import sys, torch
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
-from recguru_amd import hip
-import test_fused256_gpu as T
-torch.save(T._run_d128_inference_cases(), sys.argv[2])
-'''
-
-
-def _run_d128_inference_cases(dff=512):
-    """Encoder-inference launches of the d_model = 128 fused block: ragged M without a list, M = 20 000 with the live-tile list, the three
-    dropout modes."""
-    from recguru_amd import hip
-    dt = torch.bfloat16
-    d = 128
-    outs = []
-    for M, drop_p in ((64 * 5 + 16, 0.0), (20000, 0.0), (20000, 0.5), (20000, 0.3)):
-        ctx, x = rnd(M, d, dt=dt, seed=1), rnd(M, d, dt=dt, seed=2)
-        Wo, W1, W2 = rnd(d, d, dt=dt, scale=d ** -0.5, seed=3), rnd(dff, d, dt=dt, scale=d ** -0.5, seed=4), rnd(d, dff, dt=dt, scale=dff ** -0.5, seed=5)
-        bo, b1, b2 = (0.1 * rnd(n, dt=torch.float32, seed=6 + i) for i, n in enumerate((d, dff, d)))
-        g1, g2 = (1 + 0.1 * rnd(d, dt=torch.float32, seed=10 + i) for i in range(2))
-        be1, be2 = (0.1 * rnd(d, dt=torch.float32, seed=20 + i) for i in range(2))
-        rm = ((torch.arange(M) // 16) % 3 != 1).float().cuda() * (torch.arange(M) % 5 != 2).float().cuda()
-        out, _ = hip.post_attn_fwd(ctx, x, _pack(Wo), bo, g1, be1, _pack(W1), b1, _pack(W2), b2, g2, be2, rm, w_packed=True, drop_p=drop_p,
-                                   seed_h1=11, seed_out=12)
-        outs.append(out.float().cpu())
-    return outs
-
-
-def test_eight_wave_prototype_matches_the_four_wave_kernel(tmp_path):
-    """csrc/fused128w8.hip (RG_PA8=1, a fresh process: the switch is read once) against post_attn_fwd_kernel<bf16>: the same products in
-    the same K order and the same dropout masks; LayerNorm statistics combined from eight partial sums instead of four -- outputs within
-    a bf16 ulp or two, identical zeros on the masked rows."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    ref = _run_d128_inference_cases()
-    f = str(tmp_path / "w8.pt")
-    env = dict(os.environ, RG_PA8="1")
-    subprocess.run([sys.executable, "-c", _W8_WORKER, root, f], check=True, env=env)
-    got = torch.load(f)
-    for a, b in zip(got, ref):
-        assert bool(((a == 0) == (b == 0)).all()), "different zero pattern (row mask / dropout masks)"
-        err = float((a - b).abs().max())
-        assert err <= 0.07, err                      # values are O(1..4): one or two bf16 ulps (2^-7 .. 2^-6 relative)
-        assert float((a - b).abs().mean()) <= 2e-3
-
-
-_PIPE_WORKER = r'''
-import sys, torch
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
-import test_fused256_gpu as T
-torch.save([T._run_d128_inference_cases(dff) for dff in (256, 512, 768)], sys.argv[2])
-'''
-
-
-def test_pipelined_ffn_loop_is_bit_identical(tmp_path):
-    """post_attn_fwd_kernel<bf16, ..., PIPE> (round 5, RG_PA_PIPE=1 in a fresh process -- the switch is read once; measured no faster and
-    off by default: DESIGN.md 6a): the W2 product of chunk ch - 1 issued one matrix instruction at a time between the halves of the
-    dropout + GELU epilogue of chunk ch, g chunks alternating between the x and the ctx tile, against the plain loop: same products, same
-    accumulation order, same dropout words -- the same bits, for d_ff = 256 / 512 / 768, ragged M, the live-tile list and the three
-    dropout modes."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    ref = [_run_d128_inference_cases(dff) for dff in (256, 512, 768)]
-    f = str(tmp_path / "pipelined.pt")
-    subprocess.run([sys.executable, "-c", _PIPE_WORKER, root, f], check=True, env=dict(os.environ, RG_PA_PIPE="1"))
-    got = torch.load(f)
-    n = 0
-    for ga, ra in zip(got, ref):
-        for a, b in zip(ga, ra):
-            assert torch.equal(a, b), float((a - b).abs().max())
-            assert bool(torch.isfinite(a).all())
-            n += 1
-    assert n == 12
-
-
-_ONLINE_WORKER = r'''
-import sys, torch
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
-import test_fused256_gpu as T
-torch.save(T._run_online_item_loss_cases(), sys.argv[2])
-'''
-
-
-def _run_online_item_loss_cases():
-    from recguru_amd import hip
-    outs = []
-    for dt, d, k, V, ntok in ((torch.bfloat16, 256, 200, 5000, 3000), (torch.bfloat16, 128, 300, 900, 2000), (torch.float32, 64, 1024, 5000, 700),
-                              (torch.float32, 256, 1024, 20000, 500)):
-        assert hip.item_loss_train_supported(k, d) == 2
-        g = torch.Generator().manual_seed(k)
-        table = (torch.randn(V + 2, d, generator=g) * 0.3).to(dt).cuda()
-        h = (torch.randn(ntok, d, generator=g) * 0.5).to(dt).cuda()
-        pos = torch.randint(1, V + 1, (ntok,), generator=g).cuda()
-        neg = torch.randint(1, V + 1, (ntok * k,), generator=g).cuda()
-        mask = (torch.rand(ntok, generator=g) < 0.7).float().cuda()
-        sums = torch.zeros(2, device="cuda")
-        sums[1] = mask.sum()
-        lse = torch.empty(ntok, device="cuda")
-        coef, dh = hip.item_loss_train(h, table, pos, neg, mask, k, hip.LOSS_SAMPLED_CE, sums, lse=lse)
-        live = mask.bool()
-        outs.append([coef.view(ntok, k + 1)[live].cpu(), dh.float().cpu(), lse.cpu(), sums.cpu()])
-    return outs
-
-
-def test_item_loss_online_pipelined_equals_plain(tmp_path):
-    """item_loss_train_online2_kernel (round 5: ids by one coalesced load per 64 rows + ds_bpermute, the next batch of rows requested before
-    the current one is reduced) against the plain online kernel (RG_ITEM_ONLINE_PLAIN=1, a fresh process): every lane group sees its rows
-    in the same order, so logits, lse and dh carry the same bits; the loss sum (float atomics over blocks) agrees to rounding."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    got = _run_online_item_loss_cases()
-    f = str(tmp_path / "plain.pt")
-    subprocess.run([sys.executable, "-c", _ONLINE_WORKER, root, f], check=True, env=dict(os.environ, RG_ITEM_ONLINE_PLAIN="1"))
-    ref = torch.load(f)
-    for (c1, d1, l1, s1), (c0, d0, l0, s0) in zip(got, ref):
-        assert torch.equal(c1, c0) and torch.equal(d1, d0) and torch.equal(l1, l0)
-        assert float(s1[1]) == float(s0[1]) and abs(float(s1[0]) - float(s0[0])) <= 1e-5 * abs(float(s0[0]))
-        assert bool(torch.isfinite(c1).all()) and bool(torch.isfinite(d1).all())
 
 
 @pytest.mark.parametrize("decoder", [False, True])

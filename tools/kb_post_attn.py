@@ -1,6 +1,6 @@
 """The fused post-attention block at the bench shape (pad mask, live-tile list, dropout 0.5): encoder inference / encoder
 training / decoder training (cross stage under dropout) launches, minimum of interleaved rounds.
-  python tools/kb_post_attn.py [bf16|f32|bf16x3]        (bf16x3: RG_X3_PA_RT=4 times the 64-token form instead of the 32-token one)"""
+  python tools/kb_post_attn.py [bf16|f32|bf16x3]"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from recguru_amd import hip, synthetic
