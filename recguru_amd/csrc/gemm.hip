@@ -225,7 +225,12 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(rg_gemm_nt_args a) {
             case RG_EPI_MUL_POSMASK:
               y = ((float)aux[(size_t)m * a.ldaux + n + j] > 0.f) ? y * (a.epi_scale > 0.f ? a.epi_scale : 1.f) : 0.f;
               break;
-            case RG_EPI_GELU_GRAD: y *= gelu_grad_f((float)aux[(size_t)m * a.ldaux + n + j]); break;
+            case RG_EPI_GELU_GRAD: {             // same arithmetic as the vector path: the tier's GELU', then epi_nonzero_scale
+              const float x = (float)aux[(size_t)m * a.ldaux + n + j];
+              y *= gelu_grad_t<Precise<T>::value>(x);
+              if (a.epi_nonzero_scale > 0.f) y = x != 0.f ? y * a.epi_nonzero_scale : 0.f;
+              break;
+            }
             case RG_EPI_ADD: y += (float)aux[(size_t)m * a.ldaux + n + j]; break;
             default: break;
           }
