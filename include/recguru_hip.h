@@ -151,7 +151,12 @@ int rg_gemm_tn_plan(const rg_gemm_tn_args* args /* host */, int dtype, char* nam
  * replaces ScaledDotProductAttention.forward (Transformer/transformer.py:119-129) + the mask
  * builders get_attn_pad_mask / get_attn_subsequent_mask (:54-78) + head repeat (:157).
  * masked(q,key) = (key_ids[b,key] == pad_value) || (causal && key > q); masked scores are REPLACED
- * by -1e9 before softmax.  qkv: [B,L,3*H*32] (Q|K|V), ctx: [B,L,H*32], lse: [B,H,L] f32. */
+ * by -1e9 before softmax.  qkv: [B,L,3*H*32] (Q|K|V), ctx: [B,L,H*32], lse: [B,H,L] f32.
+ * Lengths: L <= 416 keeps one head's whole key range on chip (csrc/attention.hip); 416 < L <= 2048 runs the streaming form
+ * (csrc/attention_long.hip: 64-key blocks, online softmax; the backward is two launches, dK / dV by key block and dQ by query
+ * block, no atomics: same bits on every run and in any batch).  The streaming form takes the token-major qkv form in the three
+ * tiers with rowmask, dropout and lse as documented below; it ignores x_masked == 1 and answers RG_ERR_UNSUPPORTED to
+ * x_masked == 2, qkv_hm and the x-input form.  L > 2048: RG_ERR_UNSUPPORTED. */
 typedef struct {
   const void* qkv;
   const int64_t* key_ids; int64_t pad_value; int causal;
@@ -662,7 +667,9 @@ int rg_first_live(const float* rowmask, int B, int L, int* first, void* stream);
  * Only enc_outputs[:, -1, :] is consumed on the hot path (AutoEnc4Rec_cross.py:122,154;
  * gan_training.py:157-161): row L-1 of ScaledDotProductAttention (Transformer/transformer.py:119-129)
  * with the key-pad replace-fill.  qlast [B,H*32], kv [B,L,2*H*32] (K | V), ctx / dq [B,H*32],
- * dkv [B,L,2*H*32] fully overwritten. */
+ * dkv [B,L,2*H*32] fully overwritten.  L <= 512: every key of a lane stays in registers (straight-line code); 512 < L <= 2048:
+ * the lanes loop over the keys and recompute the scores in every pass (maximum, sum, outputs) -- same arguments, same prefix
+ * folding, same dropout index space (row L - 1 of the attention map).  L > 2048: RG_ERR_UNSUPPORTED. */
 int rg_attn_lastq_fwd(const void* qlast, const void* kv, const int64_t* key_ids, int64_t pad_value, void* ctx,
                       int B, int L, int H, float scale, float drop_p, unsigned long long seed, int dtype, void* stream,
                       const float* bkv, const int* first_live);
@@ -706,7 +713,9 @@ int rg_attn_lastq_xf_bwd(const rg_lastq_x_args* args /* host */, void* stream);
  * s[b*L+q, h] = (1/n_b) * sum_{keys j live} keep(seed, ((b*H+h)*L+q)*L+j)   (keep = 0 or 1/(1-p)),
  * n_b = number of live keys (enc_ids != pad; all L keys if none is live -- replace-fill, Q3):
  * the sum of the dropped uniform attention row of MultiHeadAttention(Q, rep(u), rep(u)) (transformer.py:259).
- * rg_seq_wsum: out[b,h,:] = sum_q s[b*L+q,h] * x[b,q,:]  (backward of that stage). */
+ * rg_seq_wsum: out[b,h,:] = sum_q s[b*L+q,h] * x[b,q,:]  (backward of that stage).
+ * Length limits: rg_cross_drop_scale L <= 2048; rg_seq_wsum keeps a sequence's s rows and its partial sums in 64 KB of LDS,
+ * (L*H + (1024/N)*H*N) floats: L <= 3072 at N = 128 / H = 4, L <= 1024 at N = 256 / H = 8 (RG_ERR_UNSUPPORTED beyond). */
 int rg_cross_drop_scale(const int64_t* enc_ids, int64_t pad_value, float* s, int B, int L, int H, float drop_p,
                         unsigned long long seed, void* stream);
 int rg_seq_wsum(const void* x, const float* s, void* out, int B, int L, int H, int N, int dtype, void* stream);

@@ -20,6 +20,9 @@
 
 #define DK 32
 #define NEG_FILL (-1e9f)
+#define RESIDENT_MAX_L 416     // longer sequences: the streaming form (csrc/attention_long.hip), L <= 2048
+int rg_attn_long_fwd(const rg_attn_args* a, int dtype, void* stream);
+int rg_attn_long_bwd(const rg_attn_bwd_args* a, int dtype, void* stream);
 
 // V operand of O^T = V^T.P^T for the stacked-accumulator slot map: lane (i = dv, g) needs
 // V[key = k0 + 4g + j][dv] (j<4) and V[key = k0 + 16 + 4g + j][dv].
@@ -1714,6 +1717,7 @@ static int launch_bwd(const rg_attn_bwd_args& a, hipStream_t s) {
 extern "C" int rg_attn_fwd(const rg_attn_args* a, int dtype, void* stream) {
   if (!a || a->B <= 0 || a->L <= 0 || a->H <= 0) return rg_set_error_msg(RG_ERR_INVALID, "attn_fwd: empty problem");
   if (a->dk != DK) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "attn_fwd: d_k must be 32");
+  if (a->L > RESIDENT_MAX_L) return rg_attn_long_fwd(a, dtype, stream);
   if (a->x) {
     if (!rg_attn_fwd_x_supported(a->d, dtype, a->drop_p) || !a->wqkv || !a->bqkv)
       return rg_set_error_msg(RG_ERR_UNSUPPORTED, "attn_fwd: the x-input form needs bf16, d_model 128, dropout 0 or 0.5, wqkv and bqkv");
@@ -1732,6 +1736,7 @@ extern "C" int rg_attn_fwd(const rg_attn_args* a, int dtype, void* stream) {
 extern "C" int rg_attn_bwd(const rg_attn_bwd_args* a, int dtype, void* stream) {
   if (!a || a->B <= 0 || a->L <= 0 || a->H <= 0) return rg_set_error_msg(RG_ERR_INVALID, "attn_bwd: empty problem");
   if (a->dk != DK) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "attn_bwd: d_k must be 32");
+  if (a->L > RESIDENT_MAX_L) return rg_attn_long_bwd(a, dtype, stream);
   if (a->qkv_hm && dtype != RG_BF16) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "attn_bwd: qkv_hm is a bf16 form");
   if (dtype == RG_BF16) return launch_bwd<__bf16>(*a, (hipStream_t)stream);
   if (dtype != RG_BF16 && a->x_masked == 2)

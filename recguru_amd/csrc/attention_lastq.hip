@@ -12,7 +12,7 @@
 #define DK 32
 #define NEG_FILL (-1e9f)
 #define MASK_BIG (-1e30f)
-#define MAXKPL 8       // keys per lane: L <= 512
+#define MAXKPL 8       // keys per lane of the straight-line form: L <= 512 (longer: the looped form below, L <= 2048)
 
 template <typename T>
 __device__ __forceinline__ void load_row32(float* o, const T* p) {
@@ -236,14 +236,172 @@ __global__ __launch_bounds__(256) void attn_lastq_bwd_kernel(const T* __restrict
   if (lane == 0) store_row32(dq + (size_t)b * P + h * DK, dqa);
 }
 
+// ---- 512 < L <= 2048: the looped form ------------------------------------------------------------------------------------
+// Same arguments, same prefix folding, same dropout index space.  The lanes stride the keys in a run-time loop and nothing
+// per key stays in registers between the passes: the scores are recomputed (a 32-term dot product) in every pass --
+// forward: maximum, sum, context; backward: maximum, sum, (dV, delta), (dK, dQ).  A key of the folded prefix is not
+// fetched: the bias rows, rounded to the tier's type as the projection would have written them, stand in.
+#define MAXL_LOOP 2048
+template <typename T>
+__device__ __forceinline__ void lastq_bias_row(float* o, const float* __restrict__ bias32) {
+#pragma unroll
+  for (int j = 0; j < 32; ++j) o[j] = (float)(T)bias32[j];
+}
+// score of one key (< L): raw dot * scale, MASK_BIG where the id is the pad value
+template <typename T>
+__device__ __forceinline__ float lastq_score1(const float* q, const T* __restrict__ krow, bool pre, float dzero, bool pad, float scale) {
+  float kr[32];
+  if (!pre) load_row32(kr, krow);
+  float d = 0.f;
+  if (!pre) {
+#pragma unroll
+    for (int j = 0; j < 32; ++j) d += q[j] * kr[j];
+  }
+  d = pre ? dzero : d;
+  return pad ? MASK_BIG : d * scale;
+}
+template <typename T>
+__device__ __forceinline__ void lastq_max_sum(const float* q, const T* __restrict__ kvb, int ldkv, int koff, const int64_t* __restrict__ ids,
+                                              int64_t pad_value, int L, int lane, float scale, int first, float dzero, float& mx, float& sum) {
+  float m = -INFINITY;
+  for (int key = lane; key < L; key += 64)
+    m = fmaxf(m, lastq_score1<T>(q, kvb + (size_t)key * ldkv + koff, key < first, dzero, ids[key] == pad_value, scale));
+  mx = wave_max(m);
+  float s = 0.f;
+  for (int key = lane; key < L; key += 64)
+    s += __expf(lastq_score1<T>(q, kvb + (size_t)key * ldkv + koff, key < first, dzero, ids[key] == pad_value, scale) - mx);
+  sum = wave_sum(s);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void attn_lastq_loop_fwd_kernel(const T* __restrict__ qlast, const T* __restrict__ kv,
+                                                                  const int64_t* __restrict__ key_ids, int64_t pad_value,
+                                                                  T* __restrict__ ctx, int B, int L, int H, float scale, DropCfg drop,
+                                                                  const float* __restrict__ bkv, const int* __restrict__ first_live) {
+  const int lane = threadIdx.x & 63;
+  const int wg = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wg >= B * H) return;
+  const int b = wg / H, h = wg % H, P = H * DK;
+  float q[32];
+  load_row32(q, qlast + (size_t)b * P + h * DK);
+  const T* kvb = kv + (size_t)b * L * 2 * P;
+  const int64_t* ids = key_ids + (size_t)b * L;
+  const bool fold = bkv != nullptr && first_live != nullptr;
+  const int first = fold ? min(first_live[b], L) : 0;
+  const float dzero = fold ? lastq_bias_dot<T>(q, bkv + h * DK) : 0.f;
+  float mx, sum;
+  lastq_max_sum<T>(q, kvb, 2 * P, h * DK, ids, pad_value, L, lane, scale, first, dzero, mx, sum);
+  const float inv = 1.f / sum;
+  const unsigned int dbase = (((unsigned int)b * H + h) * L + (L - 1)) * rg_lpad(L);   // same index space as the full kernel
+  float o[32];
+#pragma unroll
+  for (int j = 0; j < 32; ++j) o[j] = 0.f;
+  for (int key = lane; key < L; key += 64) {
+    const bool pre = key < first;
+    float p = __expf(lastq_score1<T>(q, kvb + (size_t)key * 2 * P + h * DK, pre, dzero, ids[key] == pad_value, scale) - mx) * inv;
+    if (drop.thresh) p *= rg_keep(drop, dbase + key);
+    float vr[32];
+    if (pre) lastq_bias_row<T>(vr, bkv + P + h * DK);
+    else load_row32(vr, kvb + (size_t)key * 2 * P + P + h * DK);
+#pragma unroll
+    for (int j = 0; j < 32; ++j) o[j] += p * vr[j];
+  }
+#pragma unroll
+  for (int j = 0; j < 32; ++j) o[j] = wave_sum(o[j]);
+  if (lane == 0) store_row32(ctx + (size_t)b * P + h * DK, o);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void attn_lastq_loop_bwd_kernel(const T* __restrict__ qlast, const T* __restrict__ kv,
+                                                                  const T* __restrict__ dctx, const int64_t* __restrict__ key_ids,
+                                                                  int64_t pad_value, T* __restrict__ dq, T* __restrict__ dkv,
+                                                                  int B, int L, int H, float scale, DropCfg drop,
+                                                                  const float* __restrict__ bkv, const int* __restrict__ first_live) {
+  const int lane = threadIdx.x & 63;
+  const int wg = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wg >= B * H) return;
+  const int b = wg / H, h = wg % H, P = H * DK;
+  const unsigned int dbase = (((unsigned int)b * H + h) * L + (L - 1)) * rg_lpad(L);
+  const bool fold = bkv != nullptr && first_live != nullptr;
+  const int first = fold ? min(first_live[b], L) : 0;
+  float q[32], g[32];
+  load_row32(q, qlast + (size_t)b * P + h * DK);
+  load_row32(g, dctx + (size_t)b * P + h * DK);
+  const T* kvb = kv + (size_t)b * L * 2 * P;
+  T* dkvb = dkv + (size_t)b * L * 2 * P;
+  const int64_t* ids = key_ids + (size_t)b * L;
+  const float dzero = fold ? lastq_bias_dot<T>(q, bkv + h * DK) : 0.f;       // q . bk
+  const float gzero = fold ? lastq_bias_dot<T>(g, bkv + P + h * DK) : 0.f;   // dO . bv
+  float mx, sum;
+  lastq_max_sum<T>(q, kvb, 2 * P, h * DK, ids, pad_value, L, lane, scale, first, dzero, mx, sum);
+  const bool full = mx < 0.5f * MASK_BIG;          // every key replaced: uniform row, no gradient to q / k (Q3)
+  const float inv = 1.f / sum;
+  // pass 3: dV rows and delta = sum_key p dP
+  float delta = 0.f;
+  for (int key = lane; key < L; key += 64) {
+    const bool pre = key < first;
+    const float p = __expf(lastq_score1<T>(q, kvb + (size_t)key * 2 * P + h * DK, pre, dzero, ids[key] == pad_value, scale) - mx) * inv;
+    const float ks = drop.thresh ? rg_keep(drop, dbase + key) : 1.f;
+    float d = gzero;
+    if (!pre) {
+      float vr[32];
+      load_row32(vr, kvb + (size_t)key * 2 * P + P + h * DK);
+      d = 0.f;
+#pragma unroll
+      for (int j = 0; j < 32; ++j) d += g[j] * vr[j];
+    }
+    delta += p * d * ks;
+    float dv[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) dv[j] = p * ks * g[j];
+    store_row32(dkvb + (size_t)key * 2 * P + P + h * DK, dv);
+  }
+  delta = wave_sum(delta);
+  // pass 4: dK rows and dQ
+  float dqa[32];
+#pragma unroll
+  for (int j = 0; j < 32; ++j) dqa[j] = 0.f;
+  for (int key = lane; key < L; key += 64) {
+    const bool pre = key < first;
+    const bool pad = ids[key] == pad_value;
+    const float p = __expf(lastq_score1<T>(q, kvb + (size_t)key * 2 * P + h * DK, pre, dzero, pad, scale) - mx) * inv;
+    const float ks = drop.thresh ? rg_keep(drop, dbase + key) : 1.f;
+    float kr[32], d = gzero;
+    if (pre) lastq_bias_row<T>(kr, bkv + h * DK);
+    else {
+      float vr[32];
+      load_row32(kr, kvb + (size_t)key * 2 * P + h * DK);
+      load_row32(vr, kvb + (size_t)key * 2 * P + P + h * DK);
+      d = 0.f;
+#pragma unroll
+      for (int j = 0; j < 32; ++j) d += g[j] * vr[j];
+    }
+    const float ds = (full || pad) ? 0.f : p * (d * ks - delta) * scale;
+    float dk[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) { dqa[j] += ds * kr[j]; dk[j] = ds * q[j]; }
+    store_row32(dkvb + (size_t)key * 2 * P + h * DK, dk);
+  }
+#pragma unroll
+  for (int j = 0; j < 32; ++j) dqa[j] = wave_sum(dqa[j]);
+  if (lane == 0) store_row32(dq + (size_t)b * P + h * DK, dqa);
+}
+
 extern "C" int rg_attn_lastq_fwd(const void* qlast, const void* kv, const int64_t* key_ids, int64_t pad_value, void* ctx,
                                  int B, int L, int H, float scale, float drop_p, unsigned long long seed, int dtype, void* stream,
                                  const float* bkv, const int* first_live) {
   if (B <= 0) return 0;
   const DropCfg drop = make_drop(drop_p, seed);
-  if (L > 64 * MAXKPL) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "attn_lastq: L > 512");
+  if (L > MAXL_LOOP) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "attn_lastq_fwd: L > 2048 not supported");
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((B * H + 3) / 4), block(256);
+  if (L > 64 * MAXKPL) {                     // the looped form
+    if (dtype == RG_BF16) hipLaunchKernelGGL((attn_lastq_loop_fwd_kernel<__bf16>), grid, block, 0, s, (const __bf16*)qlast, (const __bf16*)kv, key_ids, pad_value, (__bf16*)ctx, B, L, H, scale, drop, bkv, first_live);
+    else if (dtype == RG_F32) hipLaunchKernelGGL((attn_lastq_loop_fwd_kernel<float>), grid, block, 0, s, (const float*)qlast, (const float*)kv, key_ids, pad_value, (float*)ctx, B, L, H, scale, drop, bkv, first_live);
+    else return rg_set_error_msg(RG_ERR_INVALID, "attn_lastq_fwd: bad dtype");
+    RG_CHECK_LAUNCH();
+    return 0;
+  }
 #define RG_LQF(T, K) hipLaunchKernelGGL((attn_lastq_fwd_kernel<T, K>), grid, block, 0, s, (const T*)qlast, (const T*)kv, key_ids, pad_value, (T*)ctx, B, L, H, scale, drop, bkv, first_live)
 #define RG_LQF_T(T)                 \
   do {                              \
@@ -266,9 +424,16 @@ extern "C" int rg_attn_lastq_bwd(const void* qlast, const void* kv, const void* 
                                  int dtype, void* stream, const float* bkv, const int* first_live) {
   if (B <= 0) return 0;
   const DropCfg drop = make_drop(drop_p, seed);
-  if (L > 64 * MAXKPL) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "attn_lastq: L > 512");
+  if (L > MAXL_LOOP) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "attn_lastq_bwd: L > 2048 not supported");
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((B * H + 3) / 4), block(256);
+  if (L > 64 * MAXKPL) {                     // the looped form
+    if (dtype == RG_BF16) hipLaunchKernelGGL((attn_lastq_loop_bwd_kernel<__bf16>), grid, block, 0, s, (const __bf16*)qlast, (const __bf16*)kv, (const __bf16*)dctx, key_ids, pad_value, (__bf16*)dq, (__bf16*)dkv, B, L, H, scale, drop, bkv, first_live);
+    else if (dtype == RG_F32) hipLaunchKernelGGL((attn_lastq_loop_bwd_kernel<float>), grid, block, 0, s, (const float*)qlast, (const float*)kv, (const float*)dctx, key_ids, pad_value, (float*)dq, (float*)dkv, B, L, H, scale, drop, bkv, first_live);
+    else return rg_set_error_msg(RG_ERR_INVALID, "attn_lastq_bwd: bad dtype");
+    RG_CHECK_LAUNCH();
+    return 0;
+  }
 #define RG_LQB(T, K) hipLaunchKernelGGL((attn_lastq_bwd_kernel<T, K>), grid, block, 0, s, (const T*)qlast, (const T*)kv, (const T*)dctx, key_ids, pad_value, (T*)dq, (T*)dkv, B, L, H, scale, drop, bkv, first_live)
 #define RG_LQB_T(T)                 \
   do {                              \

@@ -1126,7 +1126,7 @@ extern "C" int rg_seq_wsum(const void* x, const float* s, void* out, int B, int 
   if ((N & 3) || tpr < 1 || tpr > EW_BLOCK || (EW_BLOCK % tpr) || H > 8)
     return rg_set_error_msg(RG_ERR_UNSUPPORTED, "seq_wsum: needs N/4 a divisor of the block size and H <= 8");
   const size_t smem = ((size_t)L * H + (size_t)(EW_BLOCK / tpr) * H * N) * sizeof(float);
-  if (smem > 64 * 1024) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "seq_wsum: L*H + rows*H*N floats exceed 64 KB of LDS");
+  if (smem > 64 * 1024) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "seq_wsum: L*H + rows*H*N floats exceed 64 KB of LDS (N = 128 / H = 4: L <= 3072; N = 256 / H = 8: L <= 1024)");
   if (dtype == RG_BF16) hipLaunchKernelGGL((seq_wsum_kernel<__bf16, 8>), dim3(B), dim3(EW_BLOCK), smem, st, (const __bf16*)x, s, (__bf16*)out, L, H, N);
   else if (dtype == RG_F32) hipLaunchKernelGGL((seq_wsum_kernel<float, 8>), dim3(B), dim3(EW_BLOCK), smem, st, (const float*)x, s, (float*)out, L, H, N);
   else return rg_set_error_msg(RG_ERR_INVALID, "seq_wsum: bad dtype");

@@ -506,7 +506,8 @@ def attn_fwd(qkv, key_ids, pad_value, causal, H, need_lse=True, drop_p=0.0, seed
     are all identical (the projection of an all-zero input row = the bias): a leading run of such keys is folded into one.
     bqkv (with x_masked): those rows of qkv may be UNWRITTEN -- the kernel substitutes the bias rows [3*H*32] f32.
     Head-major form: qkv [3,B,H,L,32] (gemm_nt(headmajor_L=L)) with pad_rows [3*H+1,32] (bias rows of q | k | v per head
-    and a zero row, tier dtype): K / V tiles staged by LDS-DMA (rg_attn_args.qkv_hm)."""
+    and a zero row, tier dtype): K / V tiles staged by LDS-DMA (rg_attn_args.qkv_hm).
+    416 < L <= 2048: the streaming kernels (csrc/attention_long.hip) -- token-major qkv only, no bqkv substitution."""
     hm = qkv.dim() == 5
     if hm:
         _, B, Hq, L, dk = qkv.shape

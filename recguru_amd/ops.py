@@ -653,6 +653,7 @@ FUSE_ITEM_LOSS_TRAIN = True   # rg_item_loss_train: loss, coefficients and dh fr
 FUSE_ATTN_OUT_BWD = True     # rg_attn_out_bwd (LayerNorm-1 backward + dctx product) for d_model == P == 128
 LASTQ_FROM_X = True   # rg_attn_lastq_x_* / _xf_*: the last layer's single-query attention straight from x (no K / V)
 LASTQ_FOLD_PREFIX = True
+ATTN_RESIDENT_MAX_L = 416      # rg_attn_fwd / rg_attn_bwd keep a head's key range on chip up to here; 416 < L <= 2048: the streaming form
 
 
 def _zero_rows_live(rowmask, M, x_masked, K=128, N=384):
@@ -674,7 +675,7 @@ def _qkv_attn_fwd(x2, B, L, key_ids, pad_value, causal, H, Wq, bq, Wk, bk, Wv, b
     skipped by the attention kernels (nothing downstream reads those rows)."""
     wqkv = shadow_cat((Wq, Wk, Wv))
     bqkv = bias_cat((bq, bk, bv))
-    if not need_grad and FUSE_QKV_INFERENCE and hip.attn_fwd_x_supported(x2.shape[1], _COMPUTE, drop_p):
+    if not need_grad and FUSE_QKV_INFERENCE and L <= ATTN_RESIDENT_MAX_L and hip.attn_fwd_x_supported(x2.shape[1], _COMPUTE, drop_p):
         # inference pass (the critic's encoder passes, evaluation): nothing is saved, so the projection is done INSIDE the
         # attention kernel, head by head -- no Q/K/V GEMM launch, no [M, 3P] round trip through HBM
         ctx_ = hip.attn_fwd_x(x2.view(B, L, -1), wqkv, bqkv, key_ids, pad_value, causal, H, drop_p=drop_p, seed=seed,
@@ -689,9 +690,10 @@ def _qkv_attn_fwd(x2, B, L, key_ids, pad_value, causal, H, Wq, bq, Wk, bk, Wv, b
     # positions with rowmask == 0 while staging (QKV_BIAS_ROWS_IN_ATTENTION; False: the projection writes them)
     # (allow_unwritten: the caller's consumer of ctx is list-driven too -- the fused block; the rows of ctx in padded
     # tiles are then placeholders computed from unwritten Q rows)
-    sub = live is not None and QKV_BIAS_ROWS_IN_ATTENTION and allow_unwritten and _unwritten_qkv_ok()
+    # (L > 416, the streaming attention kernels: token-major qkv with every row written -- no x-input, head-major or bias-row form)
+    sub = live is not None and QKV_BIAS_ROWS_IN_ATTENTION and allow_unwritten and _unwritten_qkv_ok() and L <= ATTN_RESIDENT_MAX_L
     if (QKV_HEAD_MAJOR and _COMPUTE == torch.bfloat16 and (H, x2.shape[1]) in ((4, 128), (8, 256)) and x2.shape[0] >= 4096
-            and 16 <= L <= 416 and (not need_grad or QKV_HEAD_MAJOR_TRAIN)):
+            and 16 <= L <= ATTN_RESIDENT_MAX_L and (not need_grad or QKV_HEAD_MAJOR_TRAIN)):
         # the projection writes q | k | v HEAD-MAJOR ([3, B, H, L, 32]: a head's K / V / Q tile is one contiguous run); the
         # attention forward fills its LDS tiles by LDS-DMA, the backward's staging loads cover whole lines
         qkv = hip.gemm_nt(x2, wqkv, bqkv, live=live, skip_dead_fill=1 if sub else 2, headmajor_L=L)
@@ -754,7 +756,7 @@ def _attn_block_bwd(dy, x2, y, saved, B, L, key_ids, pad_value, causal, H, prm, 
         dctx = hip.gemm_nt(dz, shadow(Wo, transpose=True), live=live, skip_dead_fill=True)   # attn_bwd: rowmask-driven
     # the forward's decision (same inputs; x_masked == 2: it was the fused block's forward): were the padded tiles' rows of
     # qkv left unwritten?
-    sub = (QKV_BIAS_ROWS_IN_ATTENTION and x_masked == 2 and _unwritten_qkv_ok()
+    sub = (QKV_BIAS_ROWS_IN_ATTENTION and x_masked == 2 and _unwritten_qkv_ok() and L <= ATTN_RESIDENT_MAX_L
            and _zero_rows_live(rowmask, x2.shape[0], True, d, 3 * P) is not None)
     dqkv = hip.attn_bwd(qkv if qkv.dim() == 5 else qkv.view(B, L, -1), dctx.view(B, L, P), ctx_, lse, key_ids, pad_value, causal, H,
                         drop_p=drop_p, seed=seed, rowmask=rowmask, bqkv=bias_cat((bq, bk, bv)) if sub else None)
