@@ -465,6 +465,54 @@ typedef struct {
 int rg_full_ce_supported(int d, int dtype);
 int rg_full_ce_fwd(const rg_full_ce_args* args /* host */, int train, int dtype, void* stream);
 int rg_full_ce_dw(const rg_full_ce_args* args /* host */, int dtype, void* stream);
+/* ---- sampled softmax over ONE candidate set shared by every position of the call (csrc/shared_ce.hip).  cand [C] is a
+ * strictly ascending list of table rows; for every position t with mask != 0
+ *     z_pos = h_t . E[y_t] (+ pos_bias[t]),   z_c = h_t . E[cand_c] (+ cand_bias[c]) for every c with cand_c != y_t ("accidental hits" leave the sum)
+ *     loss  = sum_t m_t (log(exp(z_pos) + sum_c exp(z_c)) - z_pos) / sums[1]
+ * The structure of rg_full_ce_* over the C gathered rows: only the 16-row tiles of the live list are computed, the [n, C] logits are
+ * never stored, no float atomics (deterministic in both libraries).
+ *   rg_shared_ce_fwd  checks cand on the host (one copy-back and a wait on the stream: strictly ascending, inside [0, rows)), gathers
+ *                     wc [C, d] = E[cand], then train = 0: lse [n] and sums[0] = sum m (lse - z_pos) (per-workgroup partials, reduced in a
+ *                     fixed order); train = 1: also, for an upstream gradient of 1, dh = (sum_c p_c E[cand_c] + (p_pos - 1) E[y_t]) m / sums[1]
+ *                     (rows of padded tiles written as zeros) and coef_pos [n] = (p_pos - 1) m / sums[1].  sums[1] = the mask count ON ENTRY
+ *                     (all-reduced under data parallelism).
+ *   rg_shared_ce_bwd  the table gradient.  Candidate route: dE[cand_c] += gout[0] / sums[1] * sum_t m_t p_{t,c} h_t, p recomputed from lse
+ *                     and wc (both from rg_shared_ce_fwd).  The walk over the live rows is split over rg_shared_ce_bwd_workspace() / (C d 4)
+ *                     workgroups per candidate tile -- a number fixed by (n, C, d) -- whose [C, d] f32 partials (dw_part) are summed in split
+ *                     order; ids are unique, so every dE element is read-modified-written by one lane.  Target route, dE[y_t] += gout[0]
+ *                     coef_pos[t] h_t: with hs given the call leaves hs [n, d] = gout[0] coef_pos[t] h_t (zeros on masked rows) and tgt [n] =
+ *                     the targets as table rows, and the caller finishes with rg_embed_scatter_bwd[_binned](hs, tgt, mask, dE, skip_row)
+ *                     -- skip_row has rg_item_loss_args' meaning there.  gout NULL = 1.
+ * dtype RG_BF16 (h, table, wc, hs bf16) or RG_X3 (f32, split bf16 operands: the bf16x3 AND the f32 tier); d in {64, 128, 256}; 1 <= C < 2^31,
+ * rows < 2^31 (tails handled).  Labels outside [0, rows) are taken as 0.  Refusals (RG_ERR_UNSUPPORTED: d, dtype; RG_ERR_INVALID: C, rows,
+ * cand, missing buffers) come before any launch. */
+typedef struct {
+  const void* h;              /* [n, d] */
+  const void* table;          /* [rows, d] */
+  const int64_t* labels;      /* [n] */
+  const int64_t* cand;        /* [C] strictly ascending, in [0, rows) */
+  const float* mask;          /* [n] */
+  const int* live16;          /* rg_live_tiles(mask, n) */
+  const float* cand_bias;     /* [C] or NULL */
+  const float* pos_bias;      /* [n] or NULL (fwd) */
+  void* wc;                   /* [C, d] dtype: out of fwd, in to bwd */
+  float* lse;                 /* [n] out of fwd, in to bwd */
+  void* dh;                   /* [n, d] training form (every row written) */
+  float* coef_pos;            /* [n] training form; in to bwd when hs is given */
+  float* partials;            /* [ceil(n / 16)] scratch of fwd */
+  float* sums;                /* [2] */
+  const float* gout;          /* [1] bwd */
+  float* dw_part;             /* scratch of bwd, rg_shared_ce_bwd_workspace(n, C, d) bytes */
+  size_t dw_part_bytes;
+  float* dE;                  /* [rows, d] f32, accumulated */
+  void* hs;                   /* [n, d] dtype or NULL (bwd) */
+  int64_t* tgt;               /* [n] with hs */
+  long long n; long long C; long long rows; int d;
+} rg_shared_ce_args;
+int rg_shared_ce_supported(int d, int dtype);
+size_t rg_shared_ce_bwd_workspace(long long n, long long C, int d);      /* 0: shape not supported */
+int rg_shared_ce_fwd(const rg_shared_ce_args* args /* host */, int train, int dtype, void* stream);
+int rg_shared_ce_bwd(const rg_shared_ce_args* args /* host */, int dtype, void* stream);
 /* nn.MSELoss()(a, b) (the overlapped-user term of the generator update, GURU/gan_training.py:28-35,:494-507) and its gradient
  * in one pass: out[0] += mean((a - b)^2); da = 2 (a - b) / n = -db for an upstream gradient of 1 (either may be NULL).
  * a, b, da, db: [n] of dtype, n % 8 == 0. */

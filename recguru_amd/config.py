@@ -44,6 +44,7 @@ class get_param(object):
         self.num_blocks = int(_opt(args, "n_blocks", _BLOCKS[self.dataset_pick]))
         self.rs_d_model, self.rs_num_blocks, self.rs_d_ff = args.d_model, self.num_blocks, args.d_ff
         self.n_negs = args.n_negs
+        self.shared_negs = int(_opt(args, "shared_negs", 0))       # > 0: one shared candidate list per reconstruction batch
         self.dataset = _DATASETS[self.dataset_pick]
         names = _DOMAINS.get(self.dataset_pick, ("wesee", "txvideo"))
         self.domain_name_a, self.domain_name_b = names

@@ -101,6 +101,7 @@ SYMBOLS = ["rg_last_error", "rg_version", "rg_gemm_nt", "rg_gemm_tn", "rg_attn_f
            "rg_dropout_gelu", "rg_add_drop_ln", "rg_cross_add_ln", "rg_embed_pe_fwd2",
            "rg_det_enabled", "rg_det_set_arenas", "rg_det_fault",
            "rg_full_ce_supported", "rg_full_ce_fwd", "rg_full_ce_dw",
+           "rg_shared_ce_supported", "rg_shared_ce_bwd_workspace", "rg_shared_ce_fwd", "rg_shared_ce_bwd",
            "rg_topk_workspace", "rg_topk_scores"]
 LOSS_SAMPLED_CE, LOSS_BPR, LOSS_BPR_SAS = 0, 1, 2
 c_ll = ctypes.c_longlong
@@ -1066,6 +1067,96 @@ def full_ce_dw(h, w, labels, mask, live, lse, sums, gout, dw):
     return dw
 
 
+class SharedCeArgs(ctypes.Structure):
+    _fields_ = [("h", c_p), ("table", c_p), ("labels", c_p), ("cand", c_p), ("mask", c_p), ("live16", c_p), ("cand_bias", c_p),
+                ("pos_bias", c_p), ("wc", c_p), ("lse", c_p), ("dh", c_p), ("coef_pos", c_p), ("partials", c_p), ("sums", c_p),
+                ("gout", c_p), ("dw_part", c_p), ("dw_part_bytes", ctypes.c_size_t), ("dE", c_p), ("hs", c_p), ("tgt", c_p),
+                ("n", c_ll), ("C", c_ll), ("rows", c_ll), ("d", c_i)]
+
+
+_SHARED_WS = {}
+
+
+def _shared_ws(dev, kind, nbytes):
+    """Scratch of shared_ce_bwd (the splits' partials, the scaled copy of h), cached per (kind, device) and grown on demand, as
+    _BIN_WS is: both are consumed inside the call that fills them."""
+    ws = _SHARED_WS.get((kind, dev))
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        _SHARED_WS[(kind, dev)] = ws
+    return ws
+
+
+def shared_ce_supported(d, h):
+    return bool(lib().rg_shared_ce_supported(int(d), _full_ce_code(h)))
+
+
+def _shared_ce_check(h, table, labels, cand, mask, cand_bias, pos_bias=None):
+    n, d = h.shape
+    assert h.is_contiguous() and table.is_contiguous() and table.dtype == h.dtype and table.dim() == 2
+    assert labels.dtype == torch.int64 and labels.numel() == n and mask.dtype == torch.float32 and mask.numel() == n
+    assert cand.dtype == torch.int64 and cand.dim() == 1 and cand.is_contiguous() and cand.device == h.device
+    assert cand_bias is None or (cand_bias.dtype == torch.float32 and cand_bias.is_contiguous() and cand_bias.numel() == cand.numel())
+    assert pos_bias is None or (pos_bias.dtype == torch.float32 and pos_bias.is_contiguous() and pos_bias.numel() == n)
+
+
+def shared_ce_fwd(h, table, labels, cand, mask, live, sums, train=True, cand_bias=None, pos_bias=None):
+    """Sampled softmax of h [n,d] over the shared candidate rows table[cand] plus each position's own target (rg_shared_ce_fwd):
+    sums[1] holds the mask count on entry, sums[0] receives sum m (lse - z_pos).  Returns (lse [n] f32, wc [C,d] = table[cand] for
+    shared_ce_bwd, dh [n,d] | None, coef_pos [n] f32 | None), the last two for an upstream gradient of 1.  cand is checked (strictly
+    ascending, inside the table) with one copy-back.  live: live_tiles(mask, n)."""
+    n, d = h.shape
+    _shared_ce_check(h, table, labels, cand, mask, cand_bias, pos_bias)
+    C = cand.numel()
+    lse = torch.empty(n, device=h.device, dtype=torch.float32)
+    wc = torch.empty(max(C, 1), d, device=h.device, dtype=h.dtype)
+    dh = torch.empty_like(h) if train else None
+    coef = torch.empty(n, device=h.device, dtype=torch.float32) if train else None
+    partials = torch.empty((n + 15) // 16, device=h.device, dtype=torch.float32)
+    a = SharedCeArgs(_p(h), _p(table), _p(labels), _p(cand) if C else None, _p(mask), _p(live), _p(cand_bias), _p(pos_bias), _p(wc),
+                     _p(lse), _p(dh), _p(coef), _p(partials), _p(sums), None, None, 0, None, None, None, n, C, table.shape[0], d)
+    _check(lib().rg_shared_ce_fwd(ctypes.byref(a), int(bool(train)), _full_ce_code(h), _stream()), "rg_shared_ce_fwd")
+    return lse, wc, dh, coef
+
+
+def shared_ce_dw(h, table_rows, labels, cand, mask, live, wc, lse, coef_pos, sums, gout, dE, cand_bias=None, target_route=True):
+    """rg_shared_ce_bwd itself: dE [rows,d] f32 += gout times the candidate rows' gradient (the split product, no atomics) and --
+    target_route -- (hs [n,d] = gout * coef_pos[t] * h_t, tgt [n] = the targets as table rows), the operands of the target rows'
+    scatter; (None, None) otherwise.  hs lives in per-device scratch: consume it before the next call."""
+    n, d = h.shape
+    C = cand.numel()
+    assert dE.dtype == torch.float32 and dE.is_contiguous() and tuple(dE.shape) == (table_rows, d)
+    fn = lib().rg_shared_ce_bwd_workspace
+    fn.restype = ctypes.c_size_t
+    fn.argtypes = [c_ll, c_ll, c_i]
+    need = int(fn(n, C, d))
+    part = _shared_ws(h.device, "part", need) if need else None          # 0: unsupported shape -- the call below says which
+    hs = tgt = None
+    if target_route and n > 0:
+        nb = n * d * h.element_size()
+        hs = _shared_ws(h.device, "hs", nb)[:nb].view(h.dtype).view(n, d)
+        tgt = torch.empty(n, device=h.device, dtype=torch.int64)
+    a = SharedCeArgs(_p(h), None, _p(labels), _p(cand), _p(mask), _p(live), _p(cand_bias), None, _p(wc), _p(lse), None,
+                     _p(coef_pos), None, _p(sums), _p(gout), _p(part), need, _p(dE), _p(hs), _p(tgt), n, C, table_rows, d)
+    _check(lib().rg_shared_ce_bwd(ctypes.byref(a), _full_ce_code(h), _stream()), "rg_shared_ce_bwd")
+    return hs, tgt
+
+
+def shared_ce_bwd(h, table_rows, labels, cand, mask, live, wc, lse, coef_pos, sums, gout, dE, skip_row=-1, cand_bias=None,
+                  target_route=True):
+    """dE [rows,d] f32 += the table gradient of shared_ce_fwd's loss times gout: the candidate rows by shared_ce_dw, then --
+    target_route -- the targets' rows by the embedding scatter on gout * coef_pos[t] * h_t (the binned form for large batches, as
+    the item loss chooses); skip_row is left out of the target route."""
+    n, d = h.shape
+    hs, tgt = shared_ce_dw(h, table_rows, labels, cand, mask, live, wc, lse, coef_pos, sums, gout, dE, cand_bias, target_route)
+    if hs is not None:
+        if n >= 65536 and embed_scatter_binned_supported(n, d, table_rows):
+            embed_scatter_bwd_binned(hs, tgt, mask, dE, skip_row)
+        else:
+            embed_scatter_bwd(hs, tgt, mask, dE, skip_row)
+    return dE
+
+
 def mse(a, b, want_grads=True):
     """mean((a - b)^2) as a [1] f32 device tensor and (da, db) for an upstream gradient of 1 (rg_mse)."""
     assert a.shape == b.shape and a.dtype == b.dtype and a.is_contiguous() and b.is_contiguous() and a.numel() % 8 == 0
@@ -1618,7 +1709,32 @@ def _work_full_ce_dw(h, w, labels, mask, live, lse, sums, gout, dw):
             (C / rows_wg + 1) * nl * (d * _esize(h) + 16) + C * d * (_esize(w) + 8))
 
 
-_WORK = {"full_ce_fwd": _work_full_ce_fwd, "full_ce_dw": _work_full_ce_dw, "attn_out_bwd": _work_attn_out_bwd, "ln_bwd": _work_ln_bwd, "gemm_tn_layer": _work_gemm_tn_layer, "item_loss_scatter_binned": _work_item_loss_scatter, "attn_lastq_x_fwd": _work_lastq_x_fwd, "attn_lastq_x_bwd": _work_lastq_x_bwd, "item_loss_train": _work_item_loss_train,
+def _work_shared_ce_fwd(h, table, labels, cand, mask, live, sums, train=True, cand_bias=None, pos_bias=None):
+    """_work_full_ce_fwd over the C gathered rows, plus their gather (read and written once) and one target row per live position."""
+    n, d = h.shape
+    C = cand.numel()
+    nl = float(mask.sum())
+    wgs = -(-int(live[0]) // (8 * (2 if d <= 128 else 1)))
+    return ("shared_ce_fwd_kernel<%s,%s>" % (_tn(h), "train" if train else "infer"), 2.0 * nl * C * d * (2 if train else 1),
+            (wgs + 2) * C * d * _esize(h) + 2 * nl * d * _esize(h) + (n * d * _esize(h) if train else 0) + n * 20)
+
+
+def _work_shared_ce_dw(h, table_rows, labels, cand, mask, live, wc, lse, coef_pos, sums, gout, dE, cand_bias=None, target_route=True):
+    """Two products per (live row, candidate); the live rows of h re-read once per candidate tile of 8 * CW 16-row tiles, the splits'
+    [C, d] f32 partials written and read once, dE's candidate rows read and written once; target_route: h read, hs written."""
+    n, d = h.shape
+    C = cand.numel()
+    nl = float(mask.sum())
+    rows_wg = 16 * 8 * (2 if d <= 128 else 1)
+    fn = lib().rg_shared_ce_bwd_workspace
+    fn.restype = ctypes.c_size_t
+    fn.argtypes = [c_ll, c_ll, c_i]
+    return ("shared_ce_dw_kernel<%s>" % _tn(h), 4.0 * nl * C * d,
+            (C / rows_wg + 1) * nl * (d * _esize(h) + 16) + 2 * int(fn(n, C, d)) + C * d * (_esize(h) + 8)
+            + (2 * n * d * _esize(h) if target_route else 0))
+
+
+_WORK = {"full_ce_fwd": _work_full_ce_fwd, "full_ce_dw": _work_full_ce_dw, "shared_ce_fwd": _work_shared_ce_fwd, "shared_ce_dw": _work_shared_ce_dw, "attn_out_bwd": _work_attn_out_bwd, "ln_bwd": _work_ln_bwd, "gemm_tn_layer": _work_gemm_tn_layer, "item_loss_scatter_binned": _work_item_loss_scatter, "attn_lastq_x_fwd": _work_lastq_x_fwd, "attn_lastq_x_bwd": _work_lastq_x_bwd, "item_loss_train": _work_item_loss_train,
          "ffn_bwd_data": _work_ffn_bwd, "attn_fwd_x": _work_attn_fwd_x, "post_attn_fwd": _work_post_attn, "gemm_nt": _work_gemm_nt, "gemm_tn": _work_gemm_tn, "attn_fwd": _work_attn_fwd, "attn_bwd": _work_attn_bwd,
          "embed_pe_fwd": _work_embed_fwd, "item_loss_fwd": _work_item_loss, "item_loss_bwd": _work_item_loss}
 _PLAIN = ["dropout_", "cross_rows", "adam_multi", "adam_multi_dev", "disc_rows", "item_loss_bwd_binned", "embed_scatter_bwd", "bcast_add_ln", "seq_sum", "colsum", "outer_posmask", "interpolate",

@@ -52,6 +52,36 @@ class SampledLogits(object):
         return ops.bpr_loss(self.h, self.table, self.pos, self.neg, mask, self.k, self.skip_row, sas=sas)
 
 
+class SharedLogits(object):
+    """Deferred logits of the positive + ONE candidate list shared by every position of the batch (cand: 1-D, strictly ascending table
+    rows).  A candidate equal to a position's own target is left out of that position's softmax."""
+
+    def __init__(self, h, table, labels, cand, skip_row=-1):
+        self.h, self.table, self.labels, self.cand, self.skip_row = h, table, labels, cand, skip_row
+
+    def loss(self, mask):
+        """Sampled softmax with label 0 and masked mean over [z_pos, z_cand minus accidental hits] -- the fused kernels of
+        csrc/shared_ce.hip, no logits stored."""
+        return ops.shared_softmax_loss(self.h, self.table, self.labels, self.cand, mask, self.skip_row)
+
+    def dense(self):
+        """The [..., 1 + C] f32 logits (column 0 the positive, then the candidates in list order; accidental hits shown as -inf),
+        forward only (no autograd graph) -- for inspection at small shapes; loss() never materialises it."""
+        from . import hip
+        d = self.h.shape[-1]
+        h2 = self.h.detach().contiguous().view(-1, d)
+        labels = self.labels.contiguous().view(-1)
+        cand = self.cand.contiguous()
+        n, C = h2.shape[0], cand.numel()
+        out, _ = hip.rank_scores(h2, ops.shadow(self.table), labels, cand.view(1, C).expand(n, C).contiguous(), want_rank=False)
+        out[:, 1:].masked_fill_(cand.view(1, C) == labels.view(n, 1), float("-inf"))
+        return out.view(tuple(self.h.shape[:-1]) + (cand.numel() + 1,))
+
+    def bpr(self, mask, sas=False):
+        raise NotImplementedError("BPR takes per-position negatives (a 2-D n_items): a shared candidate list serves the sampled "
+                                  "softmax loss only")
+
+
 class FullLogits(object):
     """Deferred logits over the whole catalogue (decoder_neg=False, the reference's `else:` branch): h @ weight.T with weight the
     item table (AutoEnc4Rec.py:228-230: [B, L, V+1]) or projection_{a|b}.weight (AutoEnc4Rec_cross.py:216-220: [B, L, V_{a|b}]).
@@ -206,7 +236,7 @@ class MyAuto4Rec_c(nn.Module):
         return self.src_emb_a.weight if domain == "a" else self.src_emb_b.weight
 
     def forward(self, enc_inputs, dec_inputs, dec_outputs, n_items, domain, mask):
-        """AutoEnc4Rec_cross.py:185-221 -> SampledLogits handle (decoder_neg branch) or FullLogits over projection_{a|b}
+        """AutoEnc4Rec_cross.py:185-221 -> SampledLogits handle (decoder_neg branch; SharedLogits when n_items is 1-D) or FullLogits over projection_{a|b}
         (the `else:` branch: V_{a|b} classes)."""
         dec_out, _, _ = self.get_dec_out(enc_inputs, dec_inputs, domain, mask)
         vocab = self.param.vocab_size_a if domain == "a" else self.param.vocab_size_b
@@ -216,6 +246,8 @@ class MyAuto4Rec_c(nn.Module):
                 raise ValueError("full-vocabulary logits need projection_%s: construct MyAuto4Rec_c with param.decoder_neg=False "
                                  "(n_negs=%d >= vocab_size_%s=%d)" % (domain, self.param.n_negs, domain, vocab))
             return FullLogits(dec_out, proj.weight, dec_outputs)
+        if torch.is_tensor(n_items) and n_items.dim() == 1:           # one candidate list shared by the batch
+            return SharedLogits(dec_out, self.item_table(domain), dec_outputs, n_items)
         return SampledLogits(dec_out, self.item_table(domain), dec_outputs, n_items, self.param.n_negs)
 
 
@@ -271,6 +303,8 @@ class MyAuto4Rec(nn.Module):
         h, _, _ = self.get_dec_out(enc_inputs, dec_inputs)
         if not (self.param.decoder_neg and self.param.n_negs < self.param.vocab_size):
             return FullLogits(h, self.src_emb.weight, dec_outputs)
+        if torch.is_tensor(n_items) and n_items.dim() == 1:           # one candidate list shared by the batch
+            return SharedLogits(h, self.src_emb.weight, dec_outputs, n_items, self.pad_index)
         return SampledLogits(h, self.src_emb.weight, dec_outputs, n_items, self.param.n_negs, self.pad_index)
 
 

@@ -1274,6 +1274,66 @@ def full_softmax_loss(h, weight, labels, mask):
 
 
 # ------------------------------------------------------------------------------------------------
+# sampled softmax over one candidate set shared by the whole batch: csrc/shared_ce.hip
+# ------------------------------------------------------------------------------------------------
+class SharedSoftmaxLoss(_Fn):
+    """sum_t m_t (log(exp(z_pos) + sum_{c: S_c != y_t} exp(z_c)) - z_pos) / sum_t m_t over the rows table[cand] shared by every position
+     without the [n, C] logits: the training-form forward leaves lse, the target coefficients and dh for an upstream
+    gradient of 1; the backward scales dh and sends the table gradient -- candidate rows by the split product, target rows by the
+    embedding scatter -- into _gt(table).  skip_row: the target route adds nothing to that row (SampledLogits' meaning)."""
+
+    @staticmethod
+    def forward(ctx, h, table, labels, cand, mask, skip_row, cand_bias, pos_bias):
+        d = h.shape[-1]
+        h2 = h.contiguous().view(-1, d)
+        n = h2.shape[0]
+        labels = labels.contiguous().view(-1)
+        cand = cand.contiguous()
+        mask = mask.reshape(-1).contiguous()
+        if cand_bias is not None:
+            cand_bias = cand_bias.to(torch.float32).contiguous().view(-1)
+        if pos_bias is not None:
+            pos_bias = pos_bias.to(torch.float32).contiguous().view(-1)
+        if not hip.shared_ce_supported(d, h2):
+            raise RuntimeError("shared softmax loss: no kernel for d_model=%d in the %s tier (csrc/shared_ce.hip: d in 64, 128, 256)"
+                               % (d, compute_tier()))
+        sums = torch.zeros(2, device=h2.device, dtype=torch.float32)
+        hip.sum_into(mask, sums[1:2])
+        if _DP is not None and _DP.world > 1:
+            _DP.global_count(sums[1:2])          # Q12: sum(l*m) / GLOBAL sum(m); grads are SUM-reduced
+        live = hip.live_tiles(mask, n)
+        train = _needs_grad(ctx)
+        lse, wc, dh1, coef = hip.shared_ce_fwd(h2, shadow(table), labels, cand, mask, live, sums, train=train, cand_bias=cand_bias,
+                                               pos_bias=pos_bias)
+        ctx.table = table
+        ctx.shape = h.shape
+        ctx.skip_row = skip_row
+        ctx.biases = (cand_bias, pos_bias)
+        ctx.consumed = not train
+        ctx.save_for_backward(h2, labels, cand, mask, live, lse, wc, sums, dh1, coef)
+        return sums[0] / sums[1]
+
+    @staticmethod
+    def backward(ctx, gout):
+        h2, labels, cand, mask, live, lse, wc, sums, dh1, coef = ctx.saved_tensors
+        cand_bias, pos_bias = ctx.biases
+        dE, ret = _gt(ctx.table)
+        g1 = gout.reshape(1).to(torch.float32).contiguous()
+        if ctx.consumed:
+            # a second backward through a retained graph (or a forward without grad mode): the training form again, from scratch
+            lse, wc, dh1, coef = hip.shared_ce_fwd(h2, shadow(ctx.table), labels, cand, mask, live, sums.clone(), train=True,
+                                                   cand_bias=cand_bias, pos_bias=pos_bias)
+        ctx.consumed = True                      # dh1 is scaled in place: it serves ONE backward
+        hip.shared_ce_bwd(h2, ctx.table.shape[0], labels, cand, mask, live, wc, lse, coef, sums, g1, dE, ctx.skip_row,
+                          cand_bias=cand_bias)
+        return hip.scale_dev(dh1, g1).view(ctx.shape), ret, None, None, None, None, None, None
+
+
+def shared_softmax_loss(h, table, labels, cand, mask, skip_row=-1, cand_bias=None, pos_bias=None):
+    return SharedSoftmaxLoss.run(h, table, labels, cand, mask, skip_row, cand_bias, pos_bias)
+
+
+# ------------------------------------------------------------------------------------------------
 # K12: MSE between the embeddings of overlapped users (gan_training.py:28-35, :494-507)
 # ------------------------------------------------------------------------------------------------
 class MseLossFn(_Fn):

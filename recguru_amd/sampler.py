@@ -79,25 +79,43 @@ class DeviceDomain(object):
         self.excl, self.excl_off = t(np.concatenate(ex) if n else np.zeros(0, np.int64)), t(exoff)
         self.val, self.test = t(np.asarray(val, dtype=np.int64)), t(np.asarray(test, dtype=np.int64))
         self.alias = None
+        self._no_excl = None
         if wf is not None:                                   # data_loader.py:251-254
             w = np.power(np.asarray(wf, dtype=np.float64), 0.75)
             w[0] = 0.0
             prob, al = alias_table(w / w.sum())
             self.alias = (t(prob), t(al))
 
-    def batch(self, users, L_enc, L_dec, eos, n_neg, seed):
+    def batch(self, users, L_enc, L_dec, eos, n_neg, seed, shared_negs=0):
         users = users.to(self.device).contiguous()
         seqs = hip.assemble_batch(self.items, self.offsets, users, L_enc, L_dec, eos)
-        n_items = hip.sample_negatives(self.excl, self.excl_off, users, n_neg, self.V, seed, self.alias)
+        if shared_negs > 0:
+            n_items = self.shared_candidates(shared_negs, seed)
+        else:
+            n_items = hip.sample_negatives(self.excl, self.excl_off, users, n_neg, self.V, seed, self.alias)
         return seqs, n_items, self.val[users], self.test[users]
+
+    def shared_candidates(self, n, seed):
+        """ONE candidate list for a whole batch (models.SharedLogits): the distinct ids among n draws over 1..V, ascending -- the
+        device sampler called for one pseudo-user whose exclusion row is empty (frequency-weighted when the domain has an alias table).
+        A position's own target may be in the list; the loss leaves it out of that position's sum."""
+        if self._no_excl is None:
+            self._no_excl = (torch.zeros(1, device=self.device, dtype=torch.int64), torch.zeros(2, device=self.device, dtype=torch.int64),
+                             torch.zeros(1, device=self.device, dtype=torch.int64))
+        ex, off, user = self._no_excl
+        return torch.unique(hip.sample_negatives(ex, off, user, int(n), self.V, seed, self.alias).view(-1))
 
 
 class DeviceLoader(object):
     """Iterates a DeviceDomain like the reference's DataLoader over pickle_loader (train: num_n * enc_maxlen
-    negatives per user; eval_n: candidate_size).  rank / world shard the users as rank::world."""
+    negatives per user; eval_n: candidate_size).  rank / world shard the users as rank::world.
+    shared_negs > 0: n_items is ONE 1-D ascending list of the distinct ids among shared_negs draws, shared by the batch, instead of
+    the [B, n_neg] per-user draws (every rank draws its own: the batch seed carries the rank)."""
 
-    def __init__(self, domain, batch_size, L_enc, L_dec, eos, n_neg, seed=0, shuffle=True, rank=0, world=1, drop_last=True):
+    def __init__(self, domain, batch_size, L_enc, L_dec, eos, n_neg, seed=0, shuffle=True, rank=0, world=1, drop_last=True,
+                 shared_negs=0):
         self.dom, self.bs, self.Le, self.Ld, self.eos, self.n_neg = domain, batch_size, L_enc, L_dec, eos, n_neg
+        self.shared_negs = int(shared_negs)
         self.users = torch.arange(rank, domain.n, world, device=domain.device)[:max(domain.n // world, 1 if world == 1 else 0)]   # equal shards (dist.shard_users)
         self.shuffle, self.seed, self.epoch, self.drop_last = shuffle, int(seed) * 1000003 + rank, 0, drop_last
         self.seed_rank = (int(seed), int(rank))
@@ -117,8 +135,11 @@ class DeviceLoader(object):
             order = order[torch.randperm(order.numel(), generator=g).to(order.device)]
         for i in range(self.nb):
             u = order[i * self.bs:(i + 1) * self.bs]
-            yield self.dom.batch(u, self.Le, self.Ld, self.eos, self.n_neg,
-                                 batch_seed(self.seed_rank[0], self.seed_rank[1], self.epoch * self.nb + i))
+            seed = batch_seed(self.seed_rank[0], self.seed_rank[1], self.epoch * self.nb + i)
+            if self.shared_negs > 0:
+                yield self.dom.batch(u, self.Le, self.Ld, self.eos, self.n_neg, seed, self.shared_negs)
+            else:
+                yield self.dom.batch(u, self.Le, self.Ld, self.eos, self.n_neg, seed)
         self.epoch += 1
 
 

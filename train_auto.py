@@ -47,6 +47,9 @@ def parse():
                         "training phase to DIR/kernels_<phase>.txt/.json, and mark every step with a roctx range for rocprofv3 --marker-trace")
     p.add_argument("--profile_steps", type=int, default=3, help="--profile: steps profiled per phase (after 2 untimed ones)")
     p.add_argument("--synthetic", type=int, default=0)
+    p.add_argument("--shared_negs", type=int, default=0,
+                   help="pre-training loader only: draw this many candidates ONCE per batch and share them among all positions "
+                        "(DESIGN.md 6e) instead of n_negs private negatives per position; 0 = off")
     p.add_argument("--epochs", type=int, default=500, help="epochs per stage (train_auto.py:101 hard-codes 500)")
     p.add_argument("--steps", type=int, default=200, help="pre-training steps")
     p.add_argument("--tune_steps", type=int, default=100, help="BPR fine-tuning steps")
@@ -81,6 +84,9 @@ def main():
         re = synthetic.TensorLoader(synthetic.make_domain(args.synthetic, V, L, param.num_train_neg, seed=2), param.batch_size, device)
         re_f = re
         seqs, val, test, _ = synthetic.make_users(args.synthetic, V, L, seed=1)
+        if param.shared_negs > 0:                                              # the pre-training loader draws on the device: one list per batch
+            ae = sampler.DeviceLoader(sampler.DeviceDomain(seqs, val, test, V, device), param.batch_size, L, L, V + 1, L * param.n_negs,
+                                      seed=1, shared_negs=param.shared_negs)
         param.candidate_size = min(param.candidate_size, V - L - 3)
         ev = sampler.DeviceEvalLoader(seqs, val, test, V, device, min(param.batch_size_val, args.synthetic), L, param.rec_maxlen,
                                       V + 1, param.candidate_size)
@@ -91,7 +97,7 @@ def main():
             item_fre = data.load_pickle(found["freq_a"][0])                 # train_auto.py:411-414
         param.vocab_size_a = param.vocab_size
         gen = lambda n, seed, **kw: data.device_loader_gen(files, param, n, "a", device, seed=seed, **kw)
-        ae = gen(param.n_negs, 1)                                           # train_auto.py:417-430
+        ae = gen(param.n_negs, 1, shared_negs=param.shared_negs)            # train_auto.py:417-430
         re = gen(param.n_bpr_neg, 2, rec=True)
         re_f = gen(param.n_bpr_neg, 3, rec=True, wf=item_fre)
         ev = data.eval_loader_gen(files, param, "a", device, wf=item_fre)

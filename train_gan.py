@@ -57,6 +57,9 @@ def parse():
                         "training phase to DIR/kernels_<phase>.txt/.json, and mark every step with a roctx range for rocprofv3 --marker-trace")
     p.add_argument("--profile_steps", type=int, default=3, help="--profile: steps profiled per phase (after 2 untimed ones)")
     p.add_argument("--synthetic", type=int, default=0, help="users per domain of generated data (0 = read data_path)")
+    p.add_argument("--shared_negs", type=int, default=0,
+                   help="reconstruction loaders only: draw this many candidates ONCE per batch and share them among all positions "
+                        "(sampled softmax over one candidate list, DESIGN.md 6e) instead of n_negs private negatives per position; 0 = off")
     return p.parse_args()
 
 
@@ -92,6 +95,14 @@ def main():
         dom_b = synthetic.make_domain(args.synthetic, param.vocab_size_b - 1, L, k, seed=2)
         mk = lambda dom: synthetic.TensorLoader(dom, param.batch_size, device, rank, world)
         ae_loaders = [mk(dom_a), mk(dom_b)]
+        if param.shared_negs > 0:                                  # the reconstruction loaders draw on the device: one list per batch
+            from recguru_amd import sampler
+
+            def mk_shared(V, seed):
+                seqs, val, test, _ = synthetic.make_users(args.synthetic, V, L, seed=seed)
+                return sampler.DeviceLoader(sampler.DeviceDomain(seqs, val, test, V, device), param.batch_size, L, L, V + 1, L * k,
+                                            seed=10 + seed, rank=rank, world=world, shared_negs=param.shared_negs)
+            ae_loaders = [mk_shared(param.vocab_size_a - 1, 1), mk_shared(param.vocab_size_b - 1, 2)]
         rec_dom = synthetic.make_domain(args.synthetic, (param.vocab_size_a if args.target_domain == "a"
                                                          else param.vocab_size_b) - 1, L, param.n_bpr_neg, seed=3)
         rec_loaders = [mk(rec_dom), mk(rec_dom)]
@@ -115,7 +126,7 @@ def main():
                 sys.exit("train_gan.py: no '%s' pickle under %s (train_gan.py:65-79 naming)" % (need, param.data_path))
         # shuffled loaders with FRESH negatives per batch (data_loader.py:276-316,455-483), on the device
         gen = lambda f, n, dom, seed, **kw: Dataloader.device_loader_gen(f, param, n, dom, device, rank, world, seed=seed, **kw)
-        ae_loaders = [gen(files["a"], k, "a", 11), gen(files["b"], k, "b", 12)]
+        ae_loaders = [gen(files["a"], k, "a", 11, shared_negs=param.shared_negs), gen(files["b"], k, "b", 12, shared_negs=param.shared_negs)]
         freq = Dataloader.load_pickle(files["freq_" + t][0])
         rec_loaders = [gen(files[t], param.n_bpr_neg, t, 13, rec=True),
                        gen(files[t], param.n_bpr_neg, t, 14, rec=True, wf=freq)]
