@@ -607,6 +607,39 @@ typedef struct {
 size_t rg_topk_workspace(int B, int d, long long n_rows, int K);  /* 0 = unsupported shape */
 int rg_topk_scores(const rg_topk_args* args /* host */, int dtype, void* stream);
 
+/* ---- top-K and exact rank over a candidate list shared by the batch (csrc/topk.hip) ---------------------------
+ * rg_topk_scores with "the catalogue" read as "the ids in rows": one ascending list of table rows, the same for all B users,
+ * walked in place (no copy of the listed rows, no [B, n_list] scores or ids).  Same score function, so a (user, row) pair has the
+ * same bits here as in rg_topk_scores, whatever the list, B or the row's place in it.  dtype, d and K as above, 1 <= n_list < 2^31,
+ * table_rows < 2^31 (the walk holds a row id in one register); anything else is RG_ERR_UNSUPPORTED.
+ *   rows          strictly ascending, each in [0, table_rows): checked on the device before anything is scored (the first offending
+ *                 position comes back in one word with the wait below); RG_ERR_INVALID names that position and its value.
+ *   rank[b]       number of ids i in rows with i != target[b], i not in row b's exclusion list and score(b, i) > score(b, target[b])
+ *                 (strictly).  target[b] is any table row, in the list or not (outside [0, table_rows): RG_ERR_UNSUPPORTED); it is
+ *                 scored either way and never excluded.  Exclusion ids that are not in rows count for nothing.
+ *   topk_ids[b]   the K ids of rows (table rows, not positions in the list) outside row b's exclusion list with the highest scores,
+ *                 score descending, ties by ascending id; fewer than K eligible: trailing slots hold id -1 and score -inf.
+ * Every call copies one word (and target, when ranks are asked for) back and waits for the stream once; a refused call launches no
+ * scoring kernel and writes no output.  No float atomics: bit-identical across repeats, batch splits and both libraries.
+ * Workspace: align256(4 B) + 256 + S B K 8 bytes, S as above, now slices of the list; it grows with neither n_list nor table_rows. */
+typedef struct {
+  const void* h;                 /* [B, d]   operand dtype */
+  const void* table;             /* [table_rows, d] operand dtype */
+  long long table_rows;
+  const int64_t* rows;           /* [n_list] strictly ascending table rows: the candidate list, shared by all B users */
+  long long n_list;
+  const int64_t* target;         /* [B] or NULL; a table row, in the list or not */
+  const int64_t* excl;           /* CSR as in rg_topk_args, or both NULL */
+  const int64_t* excl_off;
+  int64_t* topk_ids;             /* [B, K] out, or NULL when K == 0 */
+  float* topk_scores;            /* [B, K] out, or NULL */
+  int* rank;                     /* [B] out, or NULL (requires target) */
+  void* workspace; size_t workspace_bytes;
+  int B, d, K;
+} rg_topk_list_args;
+size_t rg_topk_list_workspace(int B, int d, long long n_list, int K);   /* 0 = unsupported shape */
+int rg_topk_list(const rg_topk_list_args* args /* host */, int dtype, void* stream);
+
 /* ---- fused post-attention block, forward -------------------------------------------------------------
  * y = LN(ctx.Wo^T + bo + x) [; y = LN(y + o_bcast[b])] ; out = LN(gelu(y.W1^T + b1).W2^T + b2 + y) * rowmask
  * = MultiHeadAttention tail (Transformer/transformer.py:160-161) [+ collapsed dec_enc_attn, :259, Q1]

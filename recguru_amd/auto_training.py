@@ -17,7 +17,7 @@ import torch
 from . import ops, profiling
 from .models import check_recon_handle
 from .optim import Adam
-from .training import _extend_result, _new_result, plot, seen_rows
+from .training import _extend_result, _item_list, _new_result, plot, seen_rows
 
 
 def _unwrap(model):
@@ -95,23 +95,35 @@ def evaluation(model_train, data_loader, de, param_config, k_val=None, sas=False
     return [result_freq, result_rand]
 
 
-def recommend(model, enc_in, dec_in, k, param, exclude_seen=True, sas=False):
+def item_list(among, param, device=None):
+    """training.item_list for the single-domain model: `among` sorted and unique as a 1-D int64 tensor on `device`; ValueError for
+    an empty list, non-integer ids or an id outside the items 1 .. vocab_size - 1."""
+    return _item_list(among, 1, param.vocab_size - 1, device)
+
+
+def recommend(model, enc_in, dec_in, k, param, exclude_seen=True, sas=False, among=None):
     """training.recommend for the single-domain model: the k catalogue items (ids 1 .. vocab_size - 1) that score highest against
-    the last recommender-decoder state, (ids [B, k] int64, scores [B, k] f32); with exclude_seen none of the user's own items."""
+    the last recommender-decoder state, (ids [B, k] int64, scores [B, k] f32); with exclude_seen none of the user's own items.
+    among (item ids): the k best of those ids only (hip.topk_list)."""
     if sas:
         raise NotImplementedError("SASRec scoring is outside the hot path")
     from . import hip
     m = _unwrap(model)
+    rows = None if among is None else item_list(among, param, enc_in.device)
     with torch.no_grad():
         h = m.get_embedding(enc_in, dec_in)[:, -1, :].contiguous()
     excl, off = seen_rows(enc_in, 0, param.vocab_size) if exclude_seen else (None, None)
+    if rows is not None:
+        ids, scores, _ = hip.topk_list(h, ops.shadow(m.AutoEnc.src_emb.weight), k, rows, excl=excl, excl_off=off)
+        return ids, scores
     ids, scores, _ = hip.topk_scores(h, ops.shadow(m.AutoEnc.src_emb.weight), k, 1, param.vocab_size - 1, excl=excl, excl_off=off)
     return ids, scores
 
 
-def evaluation_full(model_train, data_loader, de, param_config, k_val=None, sas=False):
+def evaluation_full(model_train, data_loader, de, param_config, k_val=None, sas=False, among=None):
     """evaluation() with unsampled metrics: the exact rank of every validation / test target among all catalogue items (the
-    full-catalogue kernel); the loader's sampled candidates are ignored.  Returns one result dict in evaluation()'s layout."""
+    full-catalogue kernel); the loader's sampled candidates are ignored.  Returns one result dict in evaluation()'s layout.
+    among (item ids): every target is ranked among those ids instead, one list for all users (the shared-set protocol)."""
     from . import hip, metrics
     if sas:
         raise NotImplementedError("SASRec scoring is outside the hot path")
@@ -122,11 +134,15 @@ def evaluation_full(model_train, data_loader, de, param_config, k_val=None, sas=
     result = _new_result(k_val)[0]
     ranks = {"eval": [], "test": []}
     table = ops.shadow(m.AutoEnc.src_emb.weight)
+    rows = None if among is None else item_list(among, param_config, de)          # normalised once for every batch
     for eval_data, test_data, _, _ in data_loader:
         for tag, data in (("eval", eval_data), ("test", test_data)):
             enc_in, dec_in, target = data[0].to(de), data[1].to(de), data[2].to(de)
             with torch.no_grad():
                 h = m.get_embedding(enc_in, dec_in)[:, -1, :].contiguous()
+            if rows is not None:
+                ranks[tag].append(hip.topk_list(h, table, 0, rows, target=target.reshape(-1))[2])
+                continue
             ranks[tag].append(hip.topk_scores(h, table, 0, 1, param_config.vocab_size - 1, target=target.reshape(-1))[2])
     host = {kk: torch.cat(v).cpu().numpy() for kk, v in ranks.items()}        # one copy of the ranks for the whole evaluation
     for k in k_val:

@@ -102,7 +102,7 @@ SYMBOLS = ["rg_last_error", "rg_version", "rg_gemm_nt", "rg_gemm_tn", "rg_attn_f
            "rg_det_enabled", "rg_det_set_arenas", "rg_det_fault",
            "rg_full_ce_supported", "rg_full_ce_fwd", "rg_full_ce_dw",
            "rg_shared_ce_supported", "rg_shared_ce_bwd_workspace", "rg_shared_ce_fwd", "rg_shared_ce_bwd",
-           "rg_topk_workspace", "rg_topk_scores"]
+           "rg_topk_workspace", "rg_topk_scores", "rg_topk_list_workspace", "rg_topk_list"]
 LOSS_SAMPLED_CE, LOSS_BPR, LOSS_BPR_SAS = 0, 1, 2
 c_ll = ctypes.c_longlong
 
@@ -922,6 +922,48 @@ def topk_scores(h, table, k, first_row, n_rows, target=None, excl=None, excl_off
     a = TopkArgs(_p(h), _p(table), first_row, n_rows, _p(target), _p(excl), _p(excl_off), _p(ids), _p(scores), _p(rank),
                  _p(ws), need, B, d, k)
     _check(lib().rg_topk_scores(ctypes.byref(a), _full_ce_code(h), _stream()), "rg_topk_scores")
+    return ids, scores, rank
+
+
+class TopkListArgs(ctypes.Structure):
+    _fields_ = [("h", c_p), ("table", c_p), ("table_rows", c_ll), ("rows", c_p), ("n_list", c_ll), ("target", c_p), ("excl", c_p),
+                ("excl_off", c_p), ("topk_ids", c_p), ("topk_scores", c_p), ("rank", c_p), ("workspace", c_p),
+                ("workspace_bytes", ctypes.c_size_t), ("B", c_i), ("d", c_i), ("K", c_i)]
+
+
+def topk_list(h, table, k, rows, target=None, excl=None, excl_off=None, want_rank=None):
+    """topk_scores with the catalogue read as the ids in rows [n_list] int64 -- strictly ascending table rows, one list for all B users
+    (rg_topk_list; the listed rows are walked in place, nothing of size [B, n_list] or [n_list, d] is stored): (ids [B,k] int64 | None,
+    scores [B,k] f32 | None, rank [B] int32 | None).  ids are table rows, not positions in the list.  target[b] is any table row, in
+    the list or not; exclusion ids outside the list count for nothing.  The library checks rows on the device and refuses a list that
+    is not strictly ascending or leaves the table (one word copied back: every call waits for the stream once)."""
+    B, d = h.shape
+    k = int(k)
+    if want_rank is None:
+        want_rank = target is not None
+    assert h.is_contiguous() and table.is_contiguous() and table.dtype == h.dtype and table.shape[1] == d
+    assert rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_cuda
+    assert (excl is None) == (excl_off is None)
+    rows = rows.contiguous()
+    n_list = rows.numel()
+    if target is not None:
+        assert target.dtype == torch.int64 and target.numel() == B
+        target = target.contiguous()
+    if excl is not None:
+        assert excl.dtype == torch.int64 and excl_off.dtype == torch.int64 and excl_off.numel() == B + 1
+        excl, excl_off = excl.contiguous(), excl_off.contiguous()
+        if excl.numel() == 0:                                               # every row empty (an empty tensor has no address)
+            excl = excl_off = None
+    fn = lib().rg_topk_list_workspace
+    fn.restype = ctypes.c_size_t
+    need = int(fn(B, d, c_ll(n_list), k))
+    ws = _tn_workspace(h.device, need, "topk") if need else None           # 0: unsupported shape -- the call below says which
+    ids = torch.empty(B, k, device=h.device, dtype=torch.int64) if k > 0 else None
+    scores = torch.empty(B, k, device=h.device, dtype=torch.float32) if k > 0 else None
+    rank = torch.empty(B, device=h.device, dtype=torch.int32) if want_rank else None
+    a = TopkListArgs(_p(h), _p(table), table.shape[0], _p(rows) if n_list else None, n_list, _p(target), _p(excl), _p(excl_off),
+                     _p(ids), _p(scores), _p(rank), _p(ws), need, B, d, k)
+    _check(lib().rg_topk_list(ctypes.byref(a), _full_ce_code(h), _stream()), "rg_topk_list")
     return ids, scores, rank
 
 

@@ -319,25 +319,63 @@ def _catalogue(param, domain):
     return 1, eos - 1, eos
 
 
-def recommend(model, enc_in, dec_in, k, param, domain="a", device=None, exclude_seen=True, sas=False):
+def _item_list(among, first, n, device):
+    """among (tensor, numpy array or list of item ids) as hip.topk_list's rows: 1-D int64 on `device`, sorted, unique; ValueError
+    for an empty list, a dtype that is not an integer one, or an id outside first .. first + n - 1."""
+    if isinstance(among, torch.Tensor):
+        t = among.detach()
+    else:
+        import numpy as np
+        arr = np.asarray(among)
+        if arr.size and arr.dtype.kind not in "iu":
+            raise ValueError("item list: ids must be integers, got dtype %s" % arr.dtype)
+        t = torch.as_tensor(arr.astype(np.int64, copy=False))
+    if t.numel() == 0:
+        raise ValueError("item list: empty")
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError("item list: ids must be integers, got dtype %s" % t.dtype)
+    t = torch.unique(t.reshape(-1).to(torch.int64))                                # sorted, duplicates gone
+    lo, hi = int(t[0]), int(t[-1])
+    if lo < first or hi > first + n - 1:
+        raise ValueError("item list: id %d is outside the item ids %d .. %d" % (lo if lo < first else hi, first, first + n - 1))
+    return t.to(device).contiguous() if device is not None else t.contiguous()
+
+
+def item_list(among, param, domain="a", device=None):
+    """A candidate list for recommend / evaluation_full(among=...): the ids of `among` (tensor, numpy array or list) sorted and
+    unique as a 1-D int64 tensor on `device` (default: where the ids are).  ValueError for an empty list, non-integer ids or an id
+    that is no item of the domain (items are 1 .. vocab_size_{a|b} - 1, _catalogue)."""
+    first, n, _ = _catalogue(param, domain)
+    return _item_list(among, first, n, device)
+
+
+def recommend(model, enc_in, dec_in, k, param, domain="a", device=None, exclude_seen=True, sas=False, among=None):
     """The k items of the whole catalogue that score highest against the last recommender-decoder state: (ids [B, k] int64,
     scores [B, k] f32), score descending, ties by ascending id; with exclude_seen none of the user's own enc_in items.  One pass
-    over the item table (hip.topk_scores); [B, vocab] is never formed.  Fewer than k eligible items: -1 / -inf fill the row."""
+    over the item table (hip.topk_scores); [B, vocab] is never formed.  Fewer than k eligible items: -1 / -inf fill the row.
+    among (item ids: tensor, array or list; item_list normalises it): the k best of those ids only, the same scores, one pass over
+    the listed rows (hip.topk_list)."""
     if sas:
         raise NotImplementedError("SASRec scoring is outside the hot path")
     from . import hip
     m = _unwrap(model)
     first, n, eos = _catalogue(param, domain)
+    rows = None if among is None else item_list(among, param, domain, enc_in.device)
     h = _last_rec_state(model, enc_in, dec_in, domain, param, device)
     excl, off = seen_rows(enc_in, param.pad_index, eos) if exclude_seen else (None, None)
+    if rows is not None:
+        ids, scores, _ = hip.topk_list(h, ops.shadow(m.item_table(domain)), k, rows, excl=excl, excl_off=off)
+        return ids, scores
     ids, scores, _ = hip.topk_scores(h, ops.shadow(m.item_table(domain)), k, first, n, excl=excl, excl_off=off)
     return ids, scores
 
 
-def evaluation_full(model_train, data_loader, de, param, k_val=None, domain="a", sas=False):
+def evaluation_full(model_train, data_loader, de, param, k_val=None, domain="a", sas=False, among=None):
     """Unsampled ranking metrics: evaluation_2's loader protocol and eval_steps loop, but the rank of every validation / test target
     is its exact rank among ALL catalogue items (items scoring strictly higher), counted by the full-catalogue kernel -- the sampled
-    candidate tensors of the batches are ignored.  Returns one result dict in the layout of evaluation_2's."""
+    candidate tensors of the batches are ignored.  Returns one result dict in the layout of evaluation_2's.
+    among (item ids): the shared-set protocol -- every target is ranked among those ids instead (one list for all users; a target
+    that is in the list is not counted against itself)."""
     from . import hip, metrics
     if sas:
         raise NotImplementedError("SASRec scoring is outside the hot path")
@@ -346,6 +384,7 @@ def evaluation_full(model_train, data_loader, de, param, k_val=None, domain="a",
     model_train.eval()
     m = _unwrap(model_train)
     first, n, _ = _catalogue(param, domain)
+    rows = None if among is None else item_list(among, param, domain, de)          # normalised once for every batch
     names = ("ht_eval", "ndcg_eval", "mrr_eval", "ht_test", "ndcg_test", "mrr_test")
     result = {str(k): {nm: [] for nm in names} for k in k_val}
     ranks = {"eval": [], "test": []}
@@ -360,7 +399,10 @@ def evaluation_full(model_train, data_loader, de, param, k_val=None, domain="a",
         for tag, data in (("eval", eval_data), ("test", test_data)):
             enc_in, dec_in, target = data[0].to(de), data[1].to(de), data[2].to(de)
             h = _last_rec_state(model_train, enc_in, dec_in, domain, param, de)
-            ranks[tag].append(hip.topk_scores(h, table, 0, first, n, target=target.reshape(-1))[2])
+            if rows is not None:
+                ranks[tag].append(hip.topk_list(h, table, 0, rows, target=target.reshape(-1))[2])
+            else:
+                ranks[tag].append(hip.topk_scores(h, table, 0, first, n, target=target.reshape(-1))[2])
     host = {kk: torch.cat(v).cpu().numpy() for kk, v in ranks.items()}        # one copy of the ranks for the whole evaluation
     for k in k_val:
         for tag in ("eval", "test"):
