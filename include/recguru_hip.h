@@ -367,6 +367,42 @@ typedef struct {
 } rg_adam_seg_dev;
 int rg_adam_multi_dev(rg_adam_seg_dev* segs /* device, updated in place */, int nsegs, double lr, double beta1, double beta2,
                       double eps, void* stream);
+/* ---- optimizer options: global-norm clipping, weight decay, non-finite skip (csrc/optim.hip) -------
+ * The control record of one optimizer step: device memory, owned by the caller, zeroed once when it is allocated.
+ * rg_grad_sqnorm_multi writes it, rg_adam_multi_dev2 reads it; the host never has to. */
+typedef struct {
+  double total_sq;    /* sum of g[i]^2 over every segment of the table */
+  float norm;         /* (float)sqrt(total_sq) */
+  float coef;         /* max_norm > 0 ? min(1, max_norm / (sqrt(total_sq) + 1e-6)) : 1 -- torch.nn.utils.clip_grad_norm_'s coefficient */
+  int skip;           /* skip_nonfinite && !isfinite(total_sq) */
+  int reserved;
+  long long skipped;  /* number of calls that set skip, since the record was zeroed */
+} rg_adam_ctl;
+/* Longest chain of dependent f32 roundings behind total_sq, for segments of at most `chunk` elements:
+ *   stage 1 (one workgroup of 256 threads per segment, f32): a thread keeps four running sums and adds (fused multiply-add, one
+ *   rounding) element after element into them, at most ceil(chunk / 1024) per sum, the scalar tail (at most one element per thread)
+ *   on top: + 1; the four sums of a thread: a tree of depth 2; the 64 lanes of a wave: depth 6; the four waves: depth 2.
+ *   stage 2 (one workgroup, double): a thread adds ceil(nsegs / 256) partials in order, then a tree of depth 8 over the threads; a
+ *   double addition rounds at 2^-53 = 2^-29 of an f32 rounding, so the whole stage counts as the last term (1 for nsegs < 2^36).
+ * Every term is non-negative, so |total_sq - exact| <= ((1 + 2^-24)^(chain + 1) - 1) * exact ~ (chain + 1) * 2^-24 * exact, the + 1
+ * being the rounding of a product g * g that is not fused (the first of each sum).  The order is fixed: equal inputs, equal bits. */
+#define RG_SQNORM_CHAIN(chunk, nsegs) \
+  (((chunk) + 1023) / 1024 + 1 + 2 + 6 + 2 + 1 + (int)(((((long long)(nsegs)) + 255) / 256 + 8) >> 29))
+/* Squared global gradient norm over the table rg_adam_multi_dev walks (steps are not touched), in two launches: partial[b] = sum of
+ * g[i]^2 over segment b, then ONE workgroup reduces partial[0 .. nsegs) and writes *ctl (skipped += skip).  max_norm <= 0 leaves
+ * coef = 1.  A gradient whose square overflows f32 (|g| > 1.8e19) counts as non-finite.  nsegs < 1, a null pointer or
+ * max_norm < 0: RG_ERR_INVALID, nothing launched. */
+int rg_grad_sqnorm_multi(const rg_adam_seg_dev* segs /* device */, int nsegs, float* partial /* device [nsegs] */,
+                         rg_adam_ctl* ctl /* device */, double max_norm, int skip_nonfinite, void* stream);
+/* rg_adam_multi_dev with three additions, in torch's order:
+ *   g_eff = ctl->coef * g                       (ctl != NULL; g itself is NOT rewritten -- torch's clip_grad_norm_ scales p.grad in place)
+ *   g_eff += weight_decay * p                   (decoupled == 0: torch.optim.Adam(weight_decay=), after the clip)
+ *   p *= 1 - lr * weight_decay                  (decoupled != 0: torch.optim.AdamW, before the Adam update)
+ * With ctl->skip set a workgroup writes nothing to p, m or v; the step count of its segment STILL advances (a skipped step counts
+ * as a step, so a host mirror of the counters stays exact without a read-back).  ctl == NULL, weight_decay == 0, decoupled == 0
+ * gives the bits of rg_adam_multi_dev.  nsegs < 1, a null table or weight_decay < 0: RG_ERR_INVALID, nothing launched. */
+int rg_adam_multi_dev2(rg_adam_seg_dev* segs /* device, updated in place */, int nsegs, double lr, double beta1, double beta2,
+                       double eps, double weight_decay, int decoupled, const rg_adam_ctl* ctl /* device, may be NULL */, void* stream);
 /* transpose: bit 0 = dst is the transpose of src; bit 1 (RG_CAST_PACK) = dst holds the logical operand M (= src or src^T)
  * [N][K] as consecutive MFMA fragments: block (n / 16, k / 32) = 64 lanes x 8 elements, lane 16 g + i = M[16 nb + i]
  * [32 kb + 8 g .. + 8], blocks ordered nb-major -- a wave's operand fragment is then one contiguous 1 KB (bf16) read.

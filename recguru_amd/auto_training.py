@@ -16,7 +16,7 @@ import torch
 
 from . import ops, profiling
 from .models import check_recon_handle
-from .optim import Adam
+from .optim import Adam, norm_of, options as adam_options
 from .training import _extend_result, _item_list, _new_result, plot, seen_rows
 
 
@@ -197,6 +197,9 @@ def train(model_train, opt, steps, data, param_config, device_i, neg_sample=True
             break
         loss_epoch = float(tot) / n_batch
         epoch_losses.append(loss_epoch)
+        gnorm = norm_of(opt)
+        if gnorm is not None:                                        # clipping on: the epoch's last gradient norm (before the clip)
+            plot.plot(param_config.result_path + "/grad_norm_%s_%s" % (loss_type, param_config.date), float(gnorm))
         if loss_type == "s_soft":
             if verbose:
                 print("Reconstruction loss after %d epochs: %f" % (epoch, loss_epoch))
@@ -234,11 +237,11 @@ def main(args_t, device_t, train_loader_ae, train_loader_re, eval_loader, loader
         raise NotImplementedError("the SASRec baseline (--sas True) is out of scope")
     MyModel = models.MyRec(device_t, args_t, wf=item_freq, dec_rec=s2b(shared), fix_enc=s2b(fix_enc), sas=False,
                            pos_train=False).to(torch.float32).to(device_t)
-    opt = blocks.ScheduledOptim(Adam(MyModel.parameters(), betas=(0.9, 0.99), eps=1e-09), 1.0, args_t.d_model,
+    opt = blocks.ScheduledOptim(Adam(MyModel.parameters(), betas=(0.9, 0.99), eps=1e-09, **adam_options(args_t)), 1.0, args_t.d_model,
                                 args_t.n_warmup_steps)
     pre, _ = train(MyModel, opt, args_t.training_steps, [train_loader_ae, train_loader_ae], args_t, device_t,
                    neg_sample=True, loss_type="s_soft", opt_type="schedule", epochs=epochs, max_steps=max_steps)
-    opt_rec = Adam(MyModel.parameters(), lr=args_t.lr_rs, betas=(0.9, 0.99), eps=1e-09)
+    opt_rec = Adam(MyModel.parameters(), lr=args_t.lr_rs, betas=(0.9, 0.99), eps=1e-09, **adam_options(args_t))
     tune, result = train(MyModel, opt_rec, int(args_t.training_steps_tune), [train_loader_re, loader_re_f], args_t,
                          device_t, neg_sample=True, loss_type="bpr", eval_loader=eval_loader,
                          epochs=tune_epochs if tune_epochs is not None else epochs, max_steps=tune_max_steps)

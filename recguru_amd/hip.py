@@ -102,7 +102,8 @@ SYMBOLS = ["rg_last_error", "rg_version", "rg_gemm_nt", "rg_gemm_tn", "rg_attn_f
            "rg_det_enabled", "rg_det_set_arenas", "rg_det_fault",
            "rg_full_ce_supported", "rg_full_ce_fwd", "rg_full_ce_dw",
            "rg_shared_ce_supported", "rg_shared_ce_bwd_workspace", "rg_shared_ce_fwd", "rg_shared_ce_bwd",
-           "rg_topk_workspace", "rg_topk_scores", "rg_topk_list_workspace", "rg_topk_list"]
+           "rg_topk_workspace", "rg_topk_scores", "rg_topk_list_workspace", "rg_topk_list",
+           "rg_grad_sqnorm_multi", "rg_adam_multi_dev2"]
 LOSS_SAMPLED_CE, LOSS_BPR, LOSS_BPR_SAS = 0, 1, 2
 c_ll = ctypes.c_longlong
 
@@ -823,6 +824,31 @@ def adam_multi_dev(seg_table_dev, nsegs, lr, beta1, beta2, eps):
     """seg_table_dev: uint8 CUDA tensor holding nsegs rg_adam_seg_dev records; their step counts advance on the device."""
     _check(lib().rg_adam_multi_dev(_vp(seg_table_dev), int(nsegs), c_d(lr), c_d(beta1), c_d(beta2), c_d(eps), _stream()),
            "rg_adam_multi_dev")
+
+
+# numpy mirror of rg_adam_ctl (32 bytes), the device-resident control record of one optimizer step
+ADAM_CTL_DTYPE = [("total_sq", "<f8"), ("norm", "<f4"), ("coef", "<f4"), ("skip", "<i4"), ("reserved", "<i4"), ("skipped", "<i8")]
+
+
+def sqnorm_chain(chunk, nsegs):
+    """RG_SQNORM_CHAIN of include/recguru_hip.h: the longest chain of dependent f32 roundings behind rg_adam_ctl.total_sq."""
+    return (chunk + 1023) // 1024 + 1 + 2 + 6 + 2 + 1 + (((nsegs + 255) // 256 + 8) >> 29)
+
+
+def grad_sqnorm_multi(seg_table_dev, nsegs, partial, ctl, max_norm=0.0, skip_nonfinite=False):
+    """seg_table_dev: nsegs rg_adam_seg_dev records; partial: float32 [>= nsegs]; ctl: uint8 CUDA tensor holding one rg_adam_ctl.
+    Two launches, no host wait: partial[b] = sum of g^2 over segment b, then *ctl (total_sq, norm, coef, skip, skipped += skip)."""
+    assert partial is None or (partial.dtype == torch.float32 and partial.is_contiguous() and partial.numel() >= nsegs)
+    assert ctl is None or (ctl.dtype == torch.uint8 and ctl.is_contiguous() and ctl.numel() >= 32)
+    _check(lib().rg_grad_sqnorm_multi(_vp(seg_table_dev), int(nsegs), _vp(partial), _vp(ctl), c_d(max_norm), int(bool(skip_nonfinite)),
+                                      _stream()), "rg_grad_sqnorm_multi")
+
+
+def adam_multi_dev2(seg_table_dev, nsegs, lr, beta1, beta2, eps, weight_decay=0.0, decoupled=False, ctl=None):
+    """adam_multi_dev with ctl's clip coefficient and skip flag (ctl: uint8 CUDA tensor holding one rg_adam_ctl, or None) and
+    coupled (torch.optim.Adam) / decoupled (torch.optim.AdamW) weight decay."""
+    _check(lib().rg_adam_multi_dev2(_vp(seg_table_dev), int(nsegs), c_d(lr), c_d(beta1), c_d(beta2), c_d(eps), c_d(weight_decay),
+                                    int(bool(decoupled)), _vp(ctl), _stream()), "rg_adam_multi_dev2")
 
 
 CAST_SEG_DTYPE = [("src", "<u8"), ("dst", "<u8"), ("R", "<i4"), ("C", "<i4"), ("ld", "<i4"), ("row_off", "<i4"),
@@ -1779,7 +1805,7 @@ def _work_shared_ce_dw(h, table_rows, labels, cand, mask, live, wc, lse, coef_po
 _WORK = {"full_ce_fwd": _work_full_ce_fwd, "full_ce_dw": _work_full_ce_dw, "shared_ce_fwd": _work_shared_ce_fwd, "shared_ce_dw": _work_shared_ce_dw, "attn_out_bwd": _work_attn_out_bwd, "ln_bwd": _work_ln_bwd, "gemm_tn_layer": _work_gemm_tn_layer, "item_loss_scatter_binned": _work_item_loss_scatter, "attn_lastq_x_fwd": _work_lastq_x_fwd, "attn_lastq_x_bwd": _work_lastq_x_bwd, "item_loss_train": _work_item_loss_train,
          "ffn_bwd_data": _work_ffn_bwd, "attn_fwd_x": _work_attn_fwd_x, "post_attn_fwd": _work_post_attn, "gemm_nt": _work_gemm_nt, "gemm_tn": _work_gemm_tn, "attn_fwd": _work_attn_fwd, "attn_bwd": _work_attn_bwd,
          "embed_pe_fwd": _work_embed_fwd, "item_loss_fwd": _work_item_loss, "item_loss_bwd": _work_item_loss}
-_PLAIN = ["dropout_", "cross_rows", "adam_multi", "adam_multi_dev", "disc_rows", "item_loss_bwd_binned", "embed_scatter_bwd", "bcast_add_ln", "seq_sum", "colsum", "outer_posmask", "interpolate",
+_PLAIN = ["dropout_", "cross_rows", "adam_multi", "adam_multi_dev", "adam_multi_dev2", "grad_sqnorm_multi", "disc_rows", "item_loss_bwd_binned", "embed_scatter_bwd", "bcast_add_ln", "seq_sum", "colsum", "outer_posmask", "interpolate",
           "gp_penalty", "sum_into", "adam", "cast", "attn_lastq_fwd", "attn_lastq_bwd", "cross_drop_scale", "seq_wsum",
           "embed_scatter_bwd_binned", "scale_dev", "dropout_gelu", "add_drop_ln", "mse", "cross_add_ln"]
 

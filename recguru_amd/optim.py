@@ -1,17 +1,80 @@
-"""Adam on the GPU through rg_adam (include/recguru_hip.h), with torch.optim.Adam's semantics as the
-reference configures it (train_gan.py:126-134, gan_training.py:359,920): no amsgrad, no weight
-decay, parameters whose .grad is None are skipped, per-parameter step counts.
+"""Adam on the GPU through rg_adam_multi_dev (include/recguru_hip.h), with torch.optim.Adam's semantics as the
+reference configures it (train_gan.py:126-134, gan_training.py:359,920): no amsgrad, parameters whose .grad is None
+are skipped, per-parameter step counts.
+
+Options beyond the reference, all off by default (csrc/optim.hip):
+  weight_decay, decoupled   torch.optim.Adam(weight_decay=) (coupled: g += wd * p) or torch.optim.AdamW (p *= 1 - lr * wd), per group.
+  max_norm                  torch.nn.utils.clip_grad_norm_ over every live parameter of every group -- EXCEPT that p.grad is not
+                            rewritten: the clipped gradient exists only inside the update (one write pass less).  Code that reads
+                            p.grad after step() sees the unclipped values.
+  skip_nonfinite            a step whose squared gradient norm is inf or NaN writes nothing to p, exp_avg or exp_avg_sq.  A SKIPPED
+                            STEP COUNTS AS A STEP: the per-parameter step counts advance as usual, so that st["step"], the host mirror
+                            of the device counters, stays exact without a read-back.  The only effect is on the bias corrections of the
+                            first few steps after a skip.
+With every option neutral step() is the code path it was: one hip.adam_multi_dev launch per group.
 """
 import torch
 
 from . import hip, ops
 
 
+def _key(live):
+    return tuple((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"]) for p, st in live)
+
+
+def _rows(live):
+    rows = []
+    for p, st in live:                                    # st["step"]: updates this parameter has had so far
+        n = p.numel()
+        for off in range(0, n, hip.ADAM_CHUNK):
+            rows.append((p.data_ptr() + 4 * off, p.grad.data_ptr() + 4 * off, st["exp_avg"].data_ptr() + 4 * off,
+                         st["exp_avg_sq"].data_ptr() + 4 * off, min(hip.ADAM_CHUNK, n - off), st["step"]))
+    return rows
+
+
+def options(param, critic=False):
+    """Constructor keywords from the run's configuration (config.get_param: weight_decay, decoupled_wd, clip_norm, skip_nonfinite).
+    Decay and clipping go to the reconstruction / recommender optimizers; critic=True (the W-GAN pair, whose balance the gradient
+    penalty sets) takes skip_nonfinite alone.  A configuration object without the attributes gives the neutral set."""
+    kw = {"skip_nonfinite": bool(getattr(param, "skip_nonfinite", False))}
+    if not critic:
+        kw.update(weight_decay=float(getattr(param, "weight_decay", 0.0)), decoupled=bool(getattr(param, "decoupled_wd", False)),
+                  max_norm=float(getattr(param, "clip_norm", 0.0)) or None)
+    return kw
+
+
+def norm_of(opt):
+    """The last measured gradient norm of an optimizer (or of the one a ScheduledOptim wraps) as a device scalar, None when it
+    does not clip."""
+    opt = getattr(opt, "_optimizer", opt)
+    return opt.grad_norm() if getattr(opt, "max_norm", None) else None
+
+
 class Adam(object):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        self.param_groups = [{"params": [p for p in params], "lr": lr, "betas": tuple(betas), "eps": eps}]
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False, max_norm=None,
+                 skip_nonfinite=False):
+        """params: an iterable of parameters, or a list of torch-style group dicts {"params": [...], and optionally "lr", "betas",
+        "eps", "weight_decay", "decoupled"}.  max_norm and skip_nonfinite belong to the optimizer: one norm over all groups."""
+        params = list(params)
+        if not params or not isinstance(params[0], dict):
+            params = [{"params": params}]
+        self.param_groups = []
+        for g in params:
+            extra = set(g) - {"params", "lr", "betas", "eps", "weight_decay", "decoupled"}
+            if extra:
+                raise ValueError("recguru_amd.optim.Adam: unknown group option(s) %s" % sorted(extra))
+            grp = {"params": [p for p in g["params"]], "lr": g.get("lr", lr), "betas": tuple(g.get("betas", betas)), "eps": g.get("eps", eps),
+                   "weight_decay": float(g.get("weight_decay", weight_decay)), "decoupled": bool(g.get("decoupled", decoupled))}
+            if grp["weight_decay"] < 0:
+                raise ValueError("recguru_amd.optim.Adam: weight_decay < 0")
+            self.param_groups.append(grp)
+        if max_norm is not None and max_norm < 0:
+            raise ValueError("recguru_amd.optim.Adam: max_norm < 0")
+        self.max_norm = None if not max_norm else float(max_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
         self.state = {}
         self._tables = {}
+        self._ctl = None                                  # device rg_adam_ctl of the option path; survives table rebuilds (the skipped counter)
 
     def zero_grad(self, set_to_none=True):
         """p.grad = None for every parameter (so step() skips what the next backward does not touch), but the
@@ -43,11 +106,49 @@ class Adam(object):
         for g, gs in zip(self.param_groups, sd.get("param_groups", [])):
             # only what step() implements is taken over; a torch.optim.Adam checkpoint that relies on anything else must not load
             # silently into different semantics
-            if gs.get("weight_decay", 0) or gs.get("amsgrad", False) or gs.get("maximize", False):
-                raise ValueError("recguru_amd.optim.Adam: weight_decay / amsgrad / maximize are not implemented (checkpoint asks for %s)"
-                                 % {k: gs[k] for k in ("weight_decay", "amsgrad", "maximize") if gs.get(k)})
+            if gs.get("amsgrad", False) or gs.get("maximize", False):
+                raise ValueError("recguru_amd.optim.Adam: amsgrad / maximize are not implemented (checkpoint asks for %s)"
+                                 % {k: gs[k] for k in ("amsgrad", "maximize") if gs.get(k)})
+            if float(gs.get("weight_decay", 0) or 0) < 0:
+                raise ValueError("recguru_amd.optim.Adam: weight_decay < 0")
             g.update({k: gs[k] for k in ("lr", "betas", "eps") if k in gs})
+            if "weight_decay" in gs:
+                g["weight_decay"] = float(gs["weight_decay"] or 0)
+            if "decoupled" in gs:                         # this class's own state_dict
+                g["decoupled"] = bool(gs["decoupled"])
+            if "decoupled_weight_decay" in gs:            # torch.optim.Adam / AdamW (torch >= 2.7 writes the key)
+                g["decoupled"] = bool(gs["decoupled_weight_decay"])
         self._tables = {}                                 # device tables are rebuilt from the restored state
+
+    def grad_norm(self):
+        """The global gradient norm the last step() measured (before clipping), a float32 device scalar; no host wait.  None before the
+        first step with an option on (only the option path measures a norm)."""
+        if self._ctl is None:
+            return None
+        return self._ctl[8:12].view(torch.float32)[0].clone()
+
+    def skipped_steps(self):
+        """Number of steps skip_nonfinite has skipped.  Reads the device counter back: the one call here that waits for the GPU."""
+        if self._ctl is None:
+            return 0
+        return int(self._ctl[24:32].view(torch.int64)[0].item())
+
+    def _neutral(self):
+        return self.max_norm is None and not self.skip_nonfinite and not any(g["weight_decay"] for g in self.param_groups)
+
+    def _live(self, g):
+        live = []
+        for p in g["params"]:
+            if p.grad is None:
+                continue
+            st = self.state.get(p)
+            if st is None:
+                st = {"step": 0, "exp_avg": torch.zeros_like(p), "exp_avg_sq": torch.zeros_like(p)}
+                self.state[p] = st
+            if not p.grad.is_contiguous():
+                p.grad = p.grad.contiguous()
+            live.append((p, st))
+        return live
 
     @torch.no_grad()
     def step(self):
@@ -56,34 +157,19 @@ class Adam(object):
         kernel itself advances -- is uploaded (from pinned memory) only when that set of parameters or one of their
         buffers changes; in steady state an optimizer step moves nothing across PCIe and never blocks the host."""
         import numpy as np
+        if not self._neutral():
+            return self._step_options()
         for gi, g in enumerate(self.param_groups):
             b1, b2 = g["betas"]
-            live = []
-            for p in g["params"]:
-                if p.grad is None:
-                    continue
-                st = self.state.get(p)
-                if st is None:
-                    st = {"step": 0, "exp_avg": torch.zeros_like(p), "exp_avg_sq": torch.zeros_like(p)}
-                    self.state[p] = st
-                if not p.grad.is_contiguous():
-                    p.grad = p.grad.contiguous()
-                live.append((p, st))
+            live = self._live(g)
             if not live:
                 continue
             # every pointer baked into the table, and the host-side step counts: state restored or edited from outside
             # (load_state_dict, a replaced exp_avg_sq, an edited step) changes the key and rebuilds the table from the host values
-            key = tuple((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"])
-                        for p, st in live)
+            key = _key(live)
             cache = self._tables.get(gi)
             if cache is None or cache["key"] != key:
-                rows = []
-                for p, st in live:                        # st["step"]: updates this parameter has had so far
-                    n = p.numel()
-                    for off in range(0, n, hip.ADAM_CHUNK):
-                        rows.append((p.data_ptr() + 4 * off, p.grad.data_ptr() + 4 * off, st["exp_avg"].data_ptr() + 4 * off,
-                                     st["exp_avg_sq"].data_ptr() + 4 * off, min(hip.ADAM_CHUNK, n - off), st["step"]))
-                tbl = np.array(rows, dtype=hip.ADAM_SEG_DEV_DTYPE)
+                tbl = np.array(_rows(live), dtype=hip.ADAM_SEG_DEV_DTYPE)
                 host = torch.from_numpy(tbl.view(np.uint8).copy()).pin_memory()
                 cache = {"key": key, "n": len(tbl), "dev": host.to(live[0][0].device, non_blocking=True), "host": host}
                 self._tables[gi] = cache
@@ -91,6 +177,56 @@ class Adam(object):
             for p, st in live:
                 st["step"] += 1                           # host mirror of the device counters (used when the table is rebuilt)
                 ops.bump(p)
-            cache["key"] = tuple((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"])
-                                 for p, st in live)      # the key the NEXT step expects (the device counters advanced with the host's)
+            cache["key"] = _key(live)                     # the key the NEXT step expects (the device counters advanced with the host's)
             ops.refresh_shadows([p for p, _ in live])
+
+    def _step_options(self):
+        """step() with an option on.  ONE segment table for all groups (group after group, so that a group's update launch walks a
+        slice of it) and beside it the partial-sum buffer; the control record is allocated once.  Launches: the norm over the whole
+        table and its finalize (rg_grad_sqnorm_multi), then one rg_adam_multi_dev2 per group.  Nothing is uploaded in steady state and
+        nothing waits: clip coefficient and skip verdict stay on the device."""
+        import numpy as np
+        lives = [self._live(g) for g in self.param_groups]
+        flat = [x for live in lives for x in live]
+        if not flat:
+            return
+        dev = flat[0][0].device
+        key = tuple(_key(live) for live in lives)
+        cache = self._tables.get("all")
+        if cache is None or cache["key"] != key:
+            rows, spans = [], []
+            for live in lives:
+                r = _rows(live)
+                spans.append((len(rows), len(r)))
+                rows += r
+            if not rows:                                  # live parameters without elements: nothing to launch
+                return
+            tbl = np.array(rows, dtype=hip.ADAM_SEG_DEV_DTYPE)
+            host = torch.from_numpy(tbl.view(np.uint8).copy()).pin_memory()
+            cache = {"key": key, "n": len(tbl), "spans": spans, "dev": host.to(dev, non_blocking=True), "host": host,
+                     "partial": torch.empty(len(tbl), device=dev, dtype=torch.float32)}
+            self._tables = {"all": cache}
+        if self._ctl is None or self._ctl.device != dev:
+            self._ctl = torch.zeros(np.dtype(hip.ADAM_CTL_DTYPE).itemsize, device=dev, dtype=torch.uint8)
+        ctl = None
+        if self.max_norm is not None or self.skip_nonfinite:
+            ctl = self._ctl
+            hip.grad_sqnorm_multi(cache["dev"], cache["n"], cache["partial"], ctl, self.max_norm or 0.0, self.skip_nonfinite)
+        rec = np.dtype(hip.ADAM_SEG_DEV_DTYPE).itemsize
+        for g, live, (first, n) in zip(self.param_groups, lives, cache["spans"]):
+            if n:
+                hip.adam_multi_dev2(cache["dev"][first * rec:], n, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
+                                    g["decoupled"], ctl)
+            for p, st in live:
+                st["step"] += 1                           # also on a skipped step: the device counters advance too
+                ops.bump(p)
+        cache["key"] = tuple(_key(live) for live in lives)
+        ops.refresh_shadows([p for p, _ in flat])
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW: Adam with decoupled weight decay, 1e-2 by default."""
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled=True, max_norm=None,
+                 skip_nonfinite=False):
+        super(AdamW, self).__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled=decoupled,
+                                    max_norm=max_norm, skip_nonfinite=skip_nonfinite)

@@ -19,7 +19,7 @@ import torch
 
 from . import ops, profiling
 from .models import check_recon_handle
-from .optim import Adam
+from .optim import Adam, norm_of, options as adam_options
 
 LAMBDA = .1         # gan_training.py:21
 CRITIC_ITERS = 5    # gan_training.py:22
@@ -232,6 +232,9 @@ def train_recon_x(model_train, opt, steps, data, param, device, neg_sample=True,
             tag = "reconstruct_loss" if loss_type == "s_soft" else "bpr_loss"
             plot.plot(param.result_path + "/%s_a_%s" % (tag, param.date), la)
             plot.plot(param.result_path + "/%s_b_%s" % (tag, param.date), lb)
+            gnorm = norm_of(opt)
+            if gnorm is not None:                                       # clipping on: this step's gradient norm (before the clip)
+                plot.plot(param.result_path + "/grad_norm_%s" % param.date, float(gnorm))
             if dp.rank == 0 and os.path.isdir(param.result_path):
                 plot.flush(param.result_path)                           # gan_training.py:890-892
             plot.tick()
@@ -606,7 +609,7 @@ def train_gan_all(netG, netD, gan_loader, opt_d, opt_g, device, param, iteration
     dp = dp or _NoDP()
     over_it = iter(train_overlap) if overlap else None                            # :373
     g_params = list(netG.parameters())
-    opt_final_rec = Adam(g_params, lr=0.001, betas=(0.9, 0.98))                  # :359
+    opt_final_rec = Adam(g_params, lr=0.001, betas=(0.9, 0.98), **adam_options(param))      # :359
     k_val = [5, 10, 20]                                                         # :361
     result = _new_result(k_val)
     a_iter, b_iter = _Cycler(gan_loader[0]), _Cycler(gan_loader[1])
@@ -691,7 +694,7 @@ def recommendation_tune(model, rec_loader, test_loader, steps, param, device, do
     it = _Cycler(rec_loader[0])
     result = _new_result(k_val)
     params = list(model.parameters())
-    opt = Adam(params, lr=0.006, betas=(0.9, 0.9))                               # :920
+    opt = Adam(params, lr=0.006, betas=(0.9, 0.9), **adam_options(param))        # :920
     losses = []
     for i in range(steps):
         restart = rec_loader[1] if (domain == "b" and i > int(steps / 2)) else rec_loader[0]
@@ -710,6 +713,8 @@ def recommendation_tune(model, rec_loader, test_loader, steps, param, device, do
             model.eval()
             print("BPR loss after %d batch" % i, float(loss.detach()))
             plot.plot(param.result_path + "/bpr_loss_%s" % domain, loss.detach())
+            if norm_of(opt) is not None:
+                plot.plot(param.result_path + "/grad_norm_tune_%s" % domain, float(norm_of(opt)))
             if test_loader is not None:
                 result_tmp = evaluation_2(model, test_loader, device, param, k_val=k_val, sas=False, domain=domain)
                 print("eval HT@10 %f, test HT@10 %f" % (result_tmp[0]["10"]["ht_eval"][0], result_tmp[0]["10"]["ht_test"][0]))

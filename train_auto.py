@@ -50,6 +50,12 @@ def parse():
     p.add_argument("--shared_negs", type=int, default=0,
                    help="pre-training loader only: draw this many candidates ONCE per batch and share them among all positions "
                         "(DESIGN.md 6e) instead of n_negs private negatives per position; 0 = off")
+    p.add_argument("--weight_decay", type=float, default=0.0, help="weight decay of both optimizers (recguru_amd/optim.py); 0 = off, as the reference")
+    p.add_argument("--decoupled_wd", type=lambda v: v == "True", default=False,
+                   help="True: AdamW's decoupled decay (p *= 1 - lr * wd); False: torch.optim.Adam's (g += wd * p)")
+    p.add_argument("--clip_norm", type=float, default=0.0, help="global gradient-norm bound of both optimizers (clip_grad_norm_ semantics); 0 = off")
+    p.add_argument("--skip_nonfinite", type=lambda v: v == "True", default=False,
+                   help="True: skip a step whose gradient norm is inf or NaN (decided on the device, no host wait)")
     p.add_argument("--epochs", type=int, default=500, help="epochs per stage (train_auto.py:101 hard-codes 500)")
     p.add_argument("--steps", type=int, default=200, help="pre-training steps")
     p.add_argument("--tune_steps", type=int, default=100, help="BPR fine-tuning steps")

@@ -60,6 +60,14 @@ def parse():
     p.add_argument("--shared_negs", type=int, default=0,
                    help="reconstruction loaders only: draw this many candidates ONCE per batch and share them among all positions "
                         "(sampled softmax over one candidate list, DESIGN.md 6e) instead of n_negs private negatives per position; 0 = off")
+    p.add_argument("--weight_decay", type=float, default=0.0,
+                   help="weight decay of the reconstruction / recommender optimizers (recguru_amd/optim.py); 0 = off, as the reference")
+    p.add_argument("--decoupled_wd", type=str2bool_par, default=False,
+                   help="True: AdamW's decoupled decay (p *= 1 - lr * wd); False: torch.optim.Adam's (g += wd * p)")
+    p.add_argument("--clip_norm", type=float, default=0.0,
+                   help="global gradient-norm bound of the reconstruction / recommender steps (clip_grad_norm_ semantics); 0 = off")
+    p.add_argument("--skip_nonfinite", type=str2bool_par, default=False,
+                   help="True: every optimizer skips a step whose gradient norm is inf or NaN (decided on the device, no host wait)")
     return p.parse_args()
 
 
@@ -70,7 +78,7 @@ def main():
         sys.exit("train_gan.py: no GPU visible -- the HIP path has no CPU fallback")
     from recguru_amd import blocks as all_module, config as param_c, data as Dataloader, dist as rdist
     from recguru_amd import models as Model, ops, synthetic, training as gt
-    from recguru_amd.optim import Adam
+    from recguru_amd.optim import Adam, options as adam_options
     if args.synthetic:
         args.vocab_size_a = args.vocab_size_a or 100000
         args.vocab_size_b = args.vocab_size_b or 100000
@@ -135,11 +143,12 @@ def main():
     torch.manual_seed(1)                                           # gan_training.py:20 (same initial weights on every rank)
     enc_model = Model.MyAuto4Rec_c(device, param, wf=None, enc_share=args.enc_share != "False",
                                    dec_rec=False).to(torch.float32).to(device)
-    opt_rec = all_module.ScheduledOptim(Adam(enc_model.parameters(), betas=(0.9, 0.98), eps=1e-09),
+    opt_rec = all_module.ScheduledOptim(Adam(enc_model.parameters(), betas=(0.9, 0.98), eps=1e-09, **adam_options(param)),
                                         1.0, param.d_model, param.n_warmup_steps)
-    opt_gen = Adam(enc_model.parameters(), lr=0.0001, betas=(0.5, 0.9))
+    # the W-GAN pair takes no decay and no clip (the gradient penalty sets that balance), only the non-finite skip
+    opt_gen = Adam(enc_model.parameters(), lr=0.0001, betas=(0.5, 0.9), **adam_options(param, critic=True))
     netD = Model.Discriminator(param.d_model, 1, param.dis_dim).to(torch.float32).to(device)
-    opt_dis = Adam(netD.parameters(), lr=0.0001, betas=(0.5, 0.9))
+    opt_dis = Adam(netD.parameters(), lr=0.0001, betas=(0.5, 0.9), **adam_options(param, critic=True))
     # per-rank random streams AFTER the (identical) initialisation: dropout masks and the gradient-penalty alpha of a
     # shard must be independent of the other shards', as the elements of one big batch are
     ops.manual_seed(1, rank)
