@@ -27,7 +27,7 @@ extern "C" {
                    is split into a bf16 pair hi + lo and a product is three bf16 MFMAs (lo.hi + hi.lo + hi.hi, f32 accumulate):
                    ~16 significant bits per operand at 3/16 of the exact-f32 matrix-pipe time.  Taken by the GEMM-class entry
                    points (rg_gemm_nt, rg_gemm_tn, rg_attn_fwd / bwd, rg_post_attn_fwd, rg_ffn_bwd_data, rg_attn_out_bwd,
-                   rg_disc_rows); everything else has no matrix product and is called with RG_F32. */
+                   rg_attn_out_bwd_cross, rg_disc_rows); everything else has no matrix product and is called with RG_F32. */
 
 #define RG_ERR_INVALID (-1)
 #define RG_ERR_UNSUPPORTED (-2)
@@ -281,7 +281,9 @@ size_t rg_ln_bwd_workspace(long long M, int N);
  * rg_bcast_add_ln: x [B*L,N] dtype, o [B,N] f32 -> y dtype, rstd f32.  rg_seq_sum: out[b,:] = sum_t x[b,t,:]. */
 int rg_bcast_add_ln(const void* x, const float* o, const float* gamma, const float* beta, void* y, float* rstd,
                     long long M, int L, int N, float eps, int dtype, void* stream);
-int rg_seq_sum(const void* x, void* out /* [B,N] dtype */, int B, int L, int N, int dtype, void* stream);
+/* rowmask [B*L] f32 or NULL: rows with rowmask == 0 are not read (they may be unwritten memory); the others are summed in the
+ * same order as without it. */
+int rg_seq_sum(const void* x, void* out /* [B,N] dtype */, int B, int L, int N, int dtype, void* stream, const float* rowmask);
 /* out[i] = (ids[i] != pad) as f32: get_pad_mask (gan_training.py:347-350) and its inline copies (:399-401, tools/utils.py:76) */
 int rg_pad_mask(const int64_t* ids, int64_t pad, float* out, long long n, void* stream);
 /* x_last[b,:] = x[b,L-1,:] ([B,d] dtype), m_last[b] = rowmask[b*L + L-1] (may be NULL): the rows the last encoder layer
@@ -771,6 +773,27 @@ typedef struct {
 } rg_attn_out_bwd_args;
 int rg_attn_out_bwd(const rg_attn_out_bwd_args* args /* host */, int dtype, void* stream);
 size_t rg_attn_out_bwd_workspace(int M);
+/* The decoder layer's form of the same launch, with the cross-attention LayerNorm backward in front (rg_ln_bwd's arithmetic on the
+ * same staged rows; y2 = LayerNorm_c(y1 + o), transformer.py:259, from its saved OUTPUT):
+ *   dy1 = LayerNorm_c backward of dy2 (y2, rstd_c, cgamma, cbeta, rowmask), rounded to the storage type and WRITTEN
+ *         (the residual gradient: rg_seq_wsum / rg_seq_sum read it),
+ *   dz  = LayerNorm-1 backward of that rounded dy1 (y1, rstd1, gamma1, beta1, the same rowmask), dctx = dz . Wo, as above.
+ * dcgamma / dcbeta / dz_colsum (optional; column sums of the UNROUNDED dy1, rg_ln_bwd's dz_colsum) and dgamma1 / dbeta1 are
+ * ACCUMULATED: per-workgroup partials (partials, >= rg_attn_out_bwd_cross_workspace(M) bytes) summed in a fixed order by a reduce
+ * launch whose threads each own one destination element -- no atomics, bit-reproducible.  live16: rows of padded tiles of dy1 /
+ * dz / dctx stay unwritten.  Replaces rg_ln_bwd + rg_attn_out_bwd on live rows bit for bit. */
+typedef struct {
+  const void* dy2; const void* y2; const float* rstd_c; const float* cgamma; const float* cbeta;
+  const void* y1; const float* rstd1; const float* gamma1; const float* beta1;
+  const float* rowmask;      /* optional [M] */
+  const void* Wot;
+  void* dy1; void* dz; void* dctx;
+  float* dcgamma; float* dcbeta; float* dz_colsum; float* dgamma1; float* dbeta1; float* partials;
+  int M, d, P, w_packed;
+  const int* live16;
+} rg_attn_out_bwd_cross_args;
+int rg_attn_out_bwd_cross(const rg_attn_out_bwd_cross_args* args /* host */, int dtype, void* stream);
+size_t rg_attn_out_bwd_cross_workspace(int M);
 int rg_ffn_bwd_data(const rg_ffn_bwd_args* args /* host */, int dtype, void* stream);
 int rg_ffn_bwd_data_supported(int d, int dff);
 /* list [1 + 2*nt + 4], nt = ceil(M/16): list[0] = number of 16-row tiles holding a row with rowmask != 0, list[1..] their
@@ -835,7 +858,8 @@ int rg_attn_lastq_xf_bwd(const rg_lastq_x_args* args /* host */, void* stream);
  * (L*H + (1024/N)*H*N) floats: L <= 3072 at N = 128 / H = 4, L <= 1024 at N = 256 / H = 8 (RG_ERR_UNSUPPORTED beyond). */
 int rg_cross_drop_scale(const int64_t* enc_ids, int64_t pad_value, float* s, int B, int L, int H, float drop_p,
                         unsigned long long seed, void* stream);
-int rg_seq_wsum(const void* x, const float* s, void* out, int B, int L, int H, int N, int dtype, void* stream);
+/* rg_seq_wsum rowmask [B*L] f32 or NULL: as for rg_seq_sum (L more floats of LDS). */
+int rg_seq_wsum(const void* x, const float* s, void* out, int B, int L, int H, int N, int dtype, void* stream, const float* rowmask);
 
 #ifdef __cplusplus
 }

@@ -590,12 +590,17 @@ __global__ __launch_bounds__(EW_BLOCK) void cross_add_ln_kernel(const T* __restr
 }
 
 // out[b,:] = sum_t x[b,t,:]   (f32 accumulation, tier-dtype result: it feeds the next GEMM)
+// rowmask: rows with rowmask == 0 are not read (unwritten rows of a list-driven producer); the others add in the same order
 template <typename T>
-__global__ __launch_bounds__(EW_BLOCK) void seq_sum_kernel(const T* __restrict__ x, T* __restrict__ out, int L, int N) {
+__global__ __launch_bounds__(EW_BLOCK) void seq_sum_kernel(const T* __restrict__ x, T* __restrict__ out, int L, int N,
+                                                          const float* __restrict__ rowmask) {
   const int b = blockIdx.x;
   for (int n = threadIdx.x; n < N; n += EW_BLOCK) {
     float s = 0.f;
-    for (int t = 0; t < L; ++t) s += (float)x[((size_t)b * L + t) * N + n];
+    for (int t = 0; t < L; ++t) {
+      if (rowmask && rowmask[(size_t)b * L + t] == 0.f) continue;
+      s += (float)x[((size_t)b * L + t) * N + n];
+    }
     out[(size_t)b * N + n] = (T)s;
   }
 }
@@ -896,15 +901,20 @@ __global__ __launch_bounds__(EW_BLOCK) void cross_drop_scale_kernel(const int64_
 }
 
 // out[b,h,:] = sum_q s[b*L+q, h] * x[b,q,:]     (one workgroup per sequence, x read once for all heads)
+// rowmask: rows with rowmask == 0 are not read (unwritten rows of a list-driven producer: 0 * NaN must not reach the sum); the
+// others add in the same order
 template <typename T, int MAXH>
 __global__ __launch_bounds__(EW_BLOCK) void seq_wsum_kernel(const T* __restrict__ x, const float* __restrict__ s, T* __restrict__ out,
-                                                           int L, int H, int N) {
-  extern __shared__ float sw_smem[];       // s[b] : L*H floats, then the [rows][H][N] partials
+                                                           int L, int H, int N, const float* __restrict__ rowmask) {
+  extern __shared__ float sw_smem[];       // s[b] : L*H floats, then the [rows][H][N] partials [, then the sequence's L mask values]
   const int b = blockIdx.x, tid = threadIdx.x;
   const int tpr = N >> 2, rows = EW_BLOCK / tpr;       // threads per row (4 columns each), rows in flight
   float* sl = sw_smem;
   float* part = sw_smem + L * H;
+  float* ml = part + rows * H * N;
   for (int i = tid; i < L * H; i += EW_BLOCK) sl[i] = s[(size_t)b * L * H + i];
+  if (rowmask)
+    for (int i = tid; i < L; i += EW_BLOCK) ml[i] = rowmask[(size_t)b * L + i];
   __syncthreads();
   const int c4 = (tid % tpr) * 4, r0 = tid / tpr;
   float acc[MAXH][4];
@@ -914,6 +924,7 @@ __global__ __launch_bounds__(EW_BLOCK) void seq_wsum_kernel(const T* __restrict_
     for (int j = 0; j < 4; ++j) acc[h][j] = 0.f;
   if (r0 < rows)
     for (int t = r0; t < L; t += rows) {
+      if (rowmask && ml[t] == 0.f) continue;
       float v[4];
       load4t(v, x + ((size_t)b * L + t) * N + c4);
 #pragma unroll
@@ -1119,16 +1130,17 @@ extern "C" int rg_cross_drop_scale(const int64_t* enc_ids, int64_t pad_value, fl
   return 0;
 }
 
-extern "C" int rg_seq_wsum(const void* x, const float* s, void* out, int B, int L, int H, int N, int dtype, void* stream) {
+extern "C" int rg_seq_wsum(const void* x, const float* s, void* out, int B, int L, int H, int N, int dtype, void* stream,
+                           const float* rowmask) {
   if (B <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int tpr = N >> 2;
   if ((N & 3) || tpr < 1 || tpr > EW_BLOCK || (EW_BLOCK % tpr) || H > 8)
     return rg_set_error_msg(RG_ERR_UNSUPPORTED, "seq_wsum: needs N/4 a divisor of the block size and H <= 8");
-  const size_t smem = ((size_t)L * H + (size_t)(EW_BLOCK / tpr) * H * N) * sizeof(float);
-  if (smem > 64 * 1024) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "seq_wsum: L*H + rows*H*N floats exceed 64 KB of LDS (N = 128 / H = 4: L <= 3072; N = 256 / H = 8: L <= 1024)");
-  if (dtype == RG_BF16) hipLaunchKernelGGL((seq_wsum_kernel<__bf16, 8>), dim3(B), dim3(EW_BLOCK), smem, st, (const __bf16*)x, s, (__bf16*)out, L, H, N);
-  else if (dtype == RG_F32) hipLaunchKernelGGL((seq_wsum_kernel<float, 8>), dim3(B), dim3(EW_BLOCK), smem, st, (const float*)x, s, (float*)out, L, H, N);
+  const size_t smem = ((size_t)L * H + (size_t)(EW_BLOCK / tpr) * H * N + (rowmask ? (size_t)L : 0)) * sizeof(float);
+  if (smem > 64 * 1024) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "seq_wsum: L*H + rows*H*N (+ L with a row mask) floats exceed 64 KB of LDS (N = 128 / H = 4: L <= 3072; N = 256 / H = 8: L <= 1024)");
+  if (dtype == RG_BF16) hipLaunchKernelGGL((seq_wsum_kernel<__bf16, 8>), dim3(B), dim3(EW_BLOCK), smem, st, (const __bf16*)x, s, (__bf16*)out, L, H, N, rowmask);
+  else if (dtype == RG_F32) hipLaunchKernelGGL((seq_wsum_kernel<float, 8>), dim3(B), dim3(EW_BLOCK), smem, st, (const float*)x, s, (float*)out, L, H, N, rowmask);
   else return rg_set_error_msg(RG_ERR_INVALID, "seq_wsum: bad dtype");
   RG_CHECK_LAUNCH();
   return 0;
@@ -1451,12 +1463,12 @@ extern "C" int rg_bcast_add_ln(const void* x, const float* o, const float* gamma
   return rg_set_error_msg(RG_ERR_INVALID, "bcast_add_ln: bad dtype");
 }
 
-extern "C" int rg_seq_sum(const void* x, void* out, int B, int L, int N, int dtype, void* stream) {
+extern "C" int rg_seq_sum(const void* x, void* out, int B, int L, int N, int dtype, void* stream, const float* rowmask) {
   if (B <= 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   DISPATCH_T(dtype,
-             hipLaunchKernelGGL(seq_sum_kernel<__bf16>, dim3(B), dim3(EW_BLOCK), 0, s, (const __bf16*)x, (__bf16*)out, L, N),
-             hipLaunchKernelGGL(seq_sum_kernel<float>, dim3(B), dim3(EW_BLOCK), 0, s, (const float*)x, (float*)out, L, N),
+             hipLaunchKernelGGL(seq_sum_kernel<__bf16>, dim3(B), dim3(EW_BLOCK), 0, s, (const __bf16*)x, (__bf16*)out, L, N, rowmask),
+             hipLaunchKernelGGL(seq_sum_kernel<float>, dim3(B), dim3(EW_BLOCK), 0, s, (const float*)x, (float*)out, L, N, rowmask),
              "seq_sum")
 }
 

@@ -1270,3 +1270,318 @@ extern "C" int rg_attn_out_bwd(const rg_attn_out_bwd_args* a, int dtype, void* s
   RG_CHECK_LAUNCH();
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The decoder layer's attention tail, backward (rg_attn_out_bwd_cross): the kernel above with the cross-attention LayerNorm
+// backward as a second row-wise stage IN FRONT, on the same staged rows (16 lanes x 8 features per row):
+//   stage C   dy1 = LayerNorm_c backward of dy2 (rg_ln_bwd's arithmetic), rounded to T where rg_ln_bwd rounds it (its store),
+//             written to HBM and kept -- rounded -- in the registers dy2 arrived in;
+//   stage 1   dz = LayerNorm-1 backward of that dy1 -> LDS (A operand) and HBM;   dctx = dz . Wo   (both as above).
+// dy1 no longer makes the round trip HBM -> attn_out_bwd, and rg_ln_bwd's pass over every row (padded tiles included) is gone.
+// Five column sums (stage C: dgamma, dbeta, sum of the unrounded dy1; stage 1: dgamma, dbeta) -> [workgroup][5][128] partials.
+// bf16: the rows of y1 are prefetched one tile ahead with dy2 / y2 (three row sets in flight under the product), all five sums
+// live in registers (250 VGPRs).  f32 / bf16x3, whose row sets and weight set are twice the registers (the kernel above already
+// sits at 232 / 244): y1 arrives in the registers of y2 once stage C is done with them, and stage C's three sums leave the
+// registers after every tile -- folded over the wave's four row groups and added to the wave's own 3 x 128 floats of LDS --
+// instead of spilling 80-odd VGPRs to scratch at the two workgroups per CU the launch is sized for.
+template <typename T>
+__global__ __launch_bounds__(256, 2) void attn_out_bwd_cross_kernel(rg_attn_out_bwd_cross_args a) {
+  constexpr int PL = FT_M * FD * 2;
+  constexpr bool PRE_Y1 = sizeof(T) == 2;
+  typedef typename LdsT<T, PL>::type LT;
+  constexpr int ACT_BYTES = FT_M * Tile<LT>::LD * (int)sizeof(LT) * LdsT<T, PL>::PLANES;
+  extern __shared__ __align__(16) unsigned char smem[];
+  LT* Adz = reinterpret_cast<LT*>(smem);
+  typedef typename ResT<T, PL>::type XT;
+  XT* Aout = reinterpret_cast<XT*>(smem + ACT_BYTES);
+  float* lnp = reinterpret_cast<float*>(smem + 2 * ACT_BYTES);      // stage C: gamma | beta | 1 / gamma, then stage 1's three
+  float* cacc = lnp + 6 * FD;                                       // !PRE_Y1: [3 sums][4 waves][128], a wave's lanes 0-15 own its rows
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lg = lane >> 4;
+  const T* __restrict__ dy2 = reinterpret_cast<const T*>(a.dy2);
+  const T* __restrict__ y2 = reinterpret_cast<const T*>(a.y2);
+  const T* __restrict__ y1 = reinterpret_cast<const T*>(a.y1);
+  T* __restrict__ dy1 = reinterpret_cast<T*>(a.dy1);
+  T* __restrict__ dz = reinterpret_cast<T*>(a.dz);
+  T* __restrict__ dctx = reinterpret_cast<T*>(a.dctx);
+  const int n0 = wave * 32;
+  const int ntiles = (a.M + FT_M - 1) / FT_M;
+  for (int i = tid; i < FD; i += 256) {
+    lnp[i] = a.cgamma[i]; lnp[FD + i] = a.cbeta[i]; lnp[2 * FD + i] = 1.f / a.cgamma[i];
+    lnp[3 * FD + i] = a.gamma1[i]; lnp[4 * FD + i] = a.beta1[i]; lnp[5 * FD + i] = 1.f / a.gamma1[i];
+  }
+  WSet<T> w;
+  load_wset(w, reinterpret_cast<const T*>(a.Wot), FD, n0, 0, li, lg, a.w_packed);
+  Frag<T> cpre[4], xpre[4], ypre[4];                    // dy2 (then: dy1, rounded), y2 (!PRE_Y1: then y1), y1 (PRE_Y1)
+  auto& yrow = [&]() -> Frag<T> (&)[4] { if constexpr (PRE_Y1) return ypre; else return xpre; }();
+  float rsc_pre[4], rs1_pre[4], rm_pre[4];
+  float dcg[8], dcb[8], dcs[8], dg[8], db[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { dcg[j] = 0.f; dcb[j] = 0.f; dcs[j] = 0.f; dg[j] = 0.f; db[j] = 0.f; }
+  LiveWalk lw;
+  lw.init(a.live16, a.M);
+  const int nwork = a.live16 ? (lw.nlive + 3) >> 2 : ntiles;
+  int cur = (int)blockIdx.x, kcur = 0;
+  auto next_group = [&](int (&g)[4]) -> bool {
+    if (cur >= nwork) {
+#pragma unroll
+      for (int rt = 0; rt < 4; ++rt) g[rt] = a.M;
+      return false;
+    }
+    if (!a.live16) {
+#pragma unroll
+      for (int rt = 0; rt < 4; ++rt) g[rt] = cur * FT_M + 16 * rt;
+    } else {
+      lw.group(kcur, g, a.M);
+    }
+    cur += gridDim.x;
+    ++kcur;
+    return true;
+  };
+  auto fetch_y1 = [&](const int (&g)[4]) {              // unconditional loads from clamped rows
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c8 = (tid & 15) * 8, m = min(g[i] + (tid >> 4), a.M - 1);
+      load_frag(yrow[i], gofs(y1, (unsigned int)(m * FD + c8)));
+      rs1_pre[i] = a.rstd1[m];
+    }
+  };
+  auto prefetch_rows = [&](const int (&g)[4]) {
+    const float* __restrict__ rmp = a.rowmask ? a.rowmask : a.rstd_c;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c8 = (tid & 15) * 8, m = min(g[i] + (tid >> 4), a.M - 1);
+      load_frag(cpre[i], gofs(dy2, (unsigned int)(m * FD + c8)));
+      load_frag(xpre[i], gofs(y2, (unsigned int)(m * FD + c8)));
+      const float rv = rmp[m];
+      rsc_pre[i] = a.rstd_c[m];
+      rm_pre[i] = a.rowmask ? rv : 1.f;
+    }
+    if constexpr (PRE_Y1) fetch_y1(g);
+  };
+  int mb[4], mbn[4];
+  bool have = next_group(mb);
+  if (have) prefetch_rows(mb);
+  if constexpr (!PRE_Y1) {
+    if (lane < 16) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) store8(cacc + (q * 4 + wave) * FD + lane * 8, dcs);       // zeros
+    }
+  }
+  __syncthreads();                                      // lnp
+  for (; have;) {
+    const bool have_next = next_group(mbn);
+    const int c8 = (tid & 15) * 8;
+    {                                                   // stage C: dy2 -> dy1
+      float gam[8], bet[8], igam[8];
+      load8(gam, lnp + c8);
+      load8(bet, lnp + FD + c8);
+      load8(igam, lnp + 2 * FD + c8);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int m = mb[i] + (tid >> 4);
+        const bool live = m < a.M;
+        const float rm = live ? rm_pre[i] : 0.f;
+        float g[8], xh[8], s1 = 0.f, s2 = 0.f;
+        if (rm != 0.f) {
+          const float irm = 1.f / rm;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const float d = (float)cpre[i].v[j] * rm;
+            xh[j] = ((float)xpre[i].v[j] * irm - bet[j]) * igam[j];
+            g[j] = d * gam[j];
+            dcg[j] += d * xh[j];
+            dcb[j] += d;
+            s1 += g[j];
+            s2 += g[j] * xh[j];
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) { g[j] = 0.f; xh[j] = 0.f; }
+        }
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+        const float rstd = rm != 0.f ? rsc_pre[i] : 0.f;
+        s1 *= 1.f / FD;
+        s2 *= 1.f / FD;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float o = rstd * (g[j] - s1 - xh[j] * s2);
+          dcs[j] += o;                                  // (rg_ln_bwd's dz_colsum: the value before it is rounded)
+          cpre[i].v[j] = (T)o;
+        }
+        if (live) {
+          if constexpr (sizeof(T) == 2) *reinterpret_cast<Frag<T>*>(gofs(dy1, (unsigned int)(m * FD + c8))) = cpre[i];
+          else store8(gofs(dy1, (unsigned int)(m * FD + c8)), cpre[i].v);
+        }
+      }
+    }
+    if constexpr (!PRE_Y1) {
+      fetch_y1(mb);                                     // into the registers y2 has left; in flight under the fold below
+#pragma unroll
+      for (int o = 16; o < 64; o <<= 1)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { dcg[j] += __shfl_xor(dcg[j], o); dcb[j] += __shfl_xor(dcb[j], o); dcs[j] += __shfl_xor(dcs[j], o); }
+      if (lane < 16) {
+        float t[8];
+        load8(t, cacc + (0 * 4 + wave) * FD + c8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) t[j] += dcg[j];
+        store8(cacc + (0 * 4 + wave) * FD + c8, t);
+        load8(t, cacc + (1 * 4 + wave) * FD + c8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) t[j] += dcb[j];
+        store8(cacc + (1 * 4 + wave) * FD + c8, t);
+        load8(t, cacc + (2 * 4 + wave) * FD + c8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) t[j] += dcs[j];
+        store8(cacc + (2 * 4 + wave) * FD + c8, t);
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { dcg[j] = 0.f; dcb[j] = 0.f; dcs[j] = 0.f; }
+    }
+    {                                                   // stage 1: dy1 -> dz
+      float gam[8], bet[8], igam[8];
+      load8(gam, lnp + 3 * FD + c8);
+      load8(bet, lnp + 4 * FD + c8);
+      load8(igam, lnp + 5 * FD + c8);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = 16 * i + (tid >> 4), m = mb[i] + (tid >> 4);
+        const bool live = m < a.M;
+        const float rm = live ? rm_pre[i] : 0.f;
+        float g[8], xh[8], s1 = 0.f, s2 = 0.f;
+        if (rm != 0.f) {
+          const float irm = 1.f / rm;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const float d = (float)cpre[i].v[j] * rm;
+            xh[j] = ((float)yrow[i].v[j] * irm - bet[j]) * igam[j];
+            g[j] = d * gam[j];
+            dg[j] += d * xh[j];
+            db[j] += d;
+            s1 += g[j];
+            s2 += g[j] * xh[j];
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) { g[j] = 0.f; xh[j] = 0.f; }
+        }
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+        const float rstd = rm != 0.f ? rs1_pre[i] : 0.f;
+        s1 *= 1.f / FD;
+        s2 *= 1.f / FD;
+        float o8[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o8[j] = rstd * (g[j] - s1 - xh[j] * s2);
+        store8(Adz + Tile<LT>::off(r, c8), o8);
+        if (live) store8(gofs(dz, (unsigned int)(m * FD + c8)), o8);
+      }
+    }
+    prefetch_rows(mbn);                                 // next tile's rows: in flight under the product
+    lds_barrier();
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int rt = 0; rt < 4; ++rt) acc[ct][rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    mma_wset<T>(acc, w, Adz, li, lg);                   // dctx = dz . Wot^T
+    regs_to_tile<XT>(acc, Aout, n0, li, lg);
+    lds_barrier();
+    tile_to_hbm<T>(Aout, dctx, FD, 0, mb, a.M, tid);
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt) mb[rt] = mbn[rt];
+    have = have_next;
+    // (barriers against the next iteration's LDS writes: as in attn_out_bwd_kernel)
+  }
+  // the five column sums: lanes with the same feature octet -> waves -> this workgroup's slice of the partials
+#pragma unroll
+  for (int o = 16; o < 64; o <<= 1)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if constexpr (PRE_Y1) { dcg[j] += __shfl_xor(dcg[j], o); dcb[j] += __shfl_xor(dcb[j], o); dcs[j] += __shfl_xor(dcs[j], o); }
+      dg[j] += __shfl_xor(dg[j], o); db[j] += __shfl_xor(db[j], o);
+    }
+  float* red = reinterpret_cast<float*>(smem);          // [5][4 waves][128]
+  __syncthreads();
+  if (lane < 16) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if constexpr (PRE_Y1) {
+        red[(0 * 4 + wave) * FD + lane * 8 + j] = dcg[j]; red[(1 * 4 + wave) * FD + lane * 8 + j] = dcb[j];
+        red[(2 * 4 + wave) * FD + lane * 8 + j] = dcs[j];
+      }
+      red[(3 * 4 + wave) * FD + lane * 8 + j] = dg[j]; red[(4 * 4 + wave) * FD + lane * 8 + j] = db[j];
+    }
+  }
+  __syncthreads();
+  for (int c = tid; c < 5 * FD; c += 256) {
+    const int q = c >> 7, n = c & (FD - 1);
+    const float* src = (!PRE_Y1 && q < 3) ? cacc : red;
+    a.partials[(size_t)blockIdx.x * 5 * FD + c] = (src[(q * 4 + 0) * FD + n] + src[(q * 4 + 1) * FD + n]) + (src[(q * 4 + 2) * FD + n] + src[(q * 4 + 3) * FD + n]);
+  }
+}
+
+// dst[n] += sum over the workgroups of partials[wg][q][n], one destination element per thread group and ONE add per element: block
+// = 16 of the 5 * 128 columns, its 16 thread rows take every 16th workgroup's partial in ascending order, their sums are added in
+// a fixed order and thread row 0 adds the total to the destination -- the same bits in every run (no float atomics; the
+// deterministic library's fixed-point shadow takes the one add through rg_acc)
+__device__ __forceinline__ void acc_once(float* p, float v) {
+#if RG_DET
+  rg_acc(p, v);
+#else
+  *p += v;
+#endif
+}
+__global__ __launch_bounds__(256) void attn_out_bwd_cross_reduce_kernel(const float* __restrict__ partials, int nblocks, float* d0, float* d1,
+                                                                        float* d2, float* d3, float* d4) {
+  __shared__ float red[16][16];
+  const int col = threadIdx.x & 15, part = threadIdx.x >> 4, c = blockIdx.x * 16 + col;   // c < 5 * FD: the grid is 5 * FD / 16
+  const int q = c >> 7;
+  float* dst = q == 0 ? d0 : (q == 1 ? d1 : (q == 2 ? d2 : (q == 3 ? d3 : d4)));           // (uniform per block: 16 | 128)
+  float s0 = 0.f, s1 = 0.f;
+  int b = part;
+  for (; b + 16 < nblocks; b += 32) {
+    s0 += partials[(size_t)b * 5 * FD + c];
+    s1 += partials[(size_t)(b + 16) * 5 * FD + c];
+  }
+  if (b < nblocks) s0 += partials[(size_t)b * 5 * FD + c];
+  red[part][col] = s0 + s1;
+  __syncthreads();
+  if (part == 0 && dst) {
+    float t = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t += red[r][col];
+    acc_once(dst + (c & (FD - 1)), t);
+  }
+}
+
+extern "C" size_t rg_attn_out_bwd_cross_workspace(int M) { return (size_t)(M <= 0 ? 0 : 512) * 5 * FD * sizeof(float); }   // (grid <= 512)
+
+extern "C" int rg_attn_out_bwd_cross(const rg_attn_out_bwd_cross_args* a, int dtype, void* stream) {
+  if (!a || a->M <= 0) return 0;
+  if (a->d != FD || a->P != FD) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "attn_out_bwd_cross: needs d_model == n_heads*32 == 128");
+  if (!a->dy2 || !a->y2 || !a->rstd_c || !a->cgamma || !a->cbeta || !a->y1 || !a->rstd1 || !a->gamma1 || !a->beta1 || !a->Wot || !a->dy1
+      || !a->dz || !a->dctx || !a->partials)
+    return rg_set_error_msg(RG_ERR_INVALID, "attn_out_bwd_cross: NULL operand");
+  if ((long long)a->M * FD * 4 >= (1ll << 32)) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "attn_out_bwd_cross: M too large for 32-bit offsets");
+  hipStream_t s = (hipStream_t)stream;
+  const int smem = 2 * act_tile_bytes(dtype, FT_M) + 6 * FD * 4 + (dtype == RG_BF16 ? 0 : 12 * FD * 4);     // (+ cacc; <= 77 KB: two per CU)
+  const int grid = attn_out_bwd_grid(a->M);
+  if (dtype == RG_BF16) {
+    hipFuncSetAttribute(reinterpret_cast<const void*>(attn_out_bwd_cross_kernel<__bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    hipLaunchKernelGGL((attn_out_bwd_cross_kernel<__bf16>), dim3(grid), dim3(256), smem, s, *a);
+  } else if (dtype == RG_F32) {
+    hipFuncSetAttribute(reinterpret_cast<const void*>(attn_out_bwd_cross_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    hipLaunchKernelGGL((attn_out_bwd_cross_kernel<float>), dim3(grid), dim3(256), smem, s, *a);
+  } else if (dtype == RG_X3) {
+    hipFuncSetAttribute(reinterpret_cast<const void*>(attn_out_bwd_cross_kernel<x3>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    hipLaunchKernelGGL((attn_out_bwd_cross_kernel<x3>), dim3(grid), dim3(256), smem, s, *a);
+  } else return rg_set_error_msg(RG_ERR_INVALID, "attn_out_bwd_cross: bad dtype");
+  if (a->dcgamma || a->dcbeta || a->dz_colsum || a->dgamma1 || a->dbeta1)
+    hipLaunchKernelGGL(attn_out_bwd_cross_reduce_kernel, dim3(5 * FD / 16), dim3(256), 0, s, a->partials, grid, a->dcgamma, a->dcbeta, a->dz_colsum,
+                       a->dgamma1, a->dbeta1);
+  RG_CHECK_LAUNCH();
+  return 0;
+}

@@ -83,6 +83,14 @@ class AttnOutBwdArgs(ctypes.Structure):
                 ("M", c_i), ("d", c_i), ("P", c_i), ("w_packed", c_i), ("live16", c_p)]
 
 
+class AttnOutBwdCrossArgs(ctypes.Structure):
+    _fields_ = [("dy2", c_p), ("y2", c_p), ("rstd_c", c_p), ("cgamma", c_p), ("cbeta", c_p),
+                ("y1", c_p), ("rstd1", c_p), ("gamma1", c_p), ("beta1", c_p), ("rowmask", c_p), ("Wot", c_p),
+                ("dy1", c_p), ("dz", c_p), ("dctx", c_p),
+                ("dcgamma", c_p), ("dcbeta", c_p), ("dz_colsum", c_p), ("dgamma1", c_p), ("dbeta1", c_p), ("partials", c_p),
+                ("M", c_i), ("d", c_i), ("P", c_i), ("w_packed", c_i), ("live16", c_p)]
+
+
 # every symbol include/recguru_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = ["rg_last_error", "rg_version", "rg_gemm_nt", "rg_gemm_tn", "rg_attn_fwd", "rg_attn_bwd",
            "rg_embed_pe_fwd", "rg_embed_pe_fwd_rows", "rg_embed_scatter_bwd", "rg_ln_bwd", "rg_bcast_add_ln", "rg_seq_sum", "rg_colsum",
@@ -94,7 +102,7 @@ SYMBOLS = ["rg_last_error", "rg_version", "rg_gemm_nt", "rg_gemm_tn", "rg_attn_f
            "rg_assemble_batch", "rg_sample_negatives", "rg_sample_negatives_alias", "rg_dropout", "rg_cross_rows", "rg_live_tiles",
            "rg_adam_multi_dev", "rg_disc_rows", "rg_disc_supported", "rg_attn_fwd_x_supported", "rg_pad_mask", "rg_last_rows",
            "rg_ffn_bwd_data", "rg_ffn_bwd_data_supported", "rg_ffn_bwd_ln_workspace", "rg_first_live",
-           "rg_attn_out_bwd", "rg_attn_out_bwd_workspace",
+           "rg_attn_out_bwd", "rg_attn_out_bwd_workspace", "rg_attn_out_bwd_cross", "rg_attn_out_bwd_cross_workspace",
            "rg_item_loss_train_supported", "rg_item_loss_train", "rg_item_loss_scatter_binned", "rg_scale_dev",
            "rg_attn_lastq_x_supported", "rg_attn_lastq_x_fwd", "rg_attn_lastq_x_bwd", "rg_attn_lastq_xf_fwd", "rg_attn_lastq_xf_bwd",
            "rg_embed_scatter_binned_workspace", "rg_embed_scatter_bwd_binned", "rg_embed_pe_fwd_split", "rg_mse",
@@ -730,11 +738,13 @@ def last_rows(x, rowmask):
     return xl, ml
 
 
-def seq_sum(x, B, L):
+def seq_sum(x, B, L, rowmask=None):
+    """out[b] = sum_t x[b, t]; rowmask [B*L] f32: rows with rowmask == 0 are not read (they may be unwritten)."""
     N = x.shape[-1]
     assert x.is_contiguous()
+    assert rowmask is None or (rowmask.dtype == torch.float32 and rowmask.numel() == B * L and rowmask.is_contiguous())
     out = torch.empty(B, N, device=x.device, dtype=x.dtype)
-    _check(lib().rg_seq_sum(_vp(x), _vp(out), B, L, N, dt_of(x), _stream()), "rg_seq_sum")
+    _check(lib().rg_seq_sum(_vp(x), _vp(out), B, L, N, dt_of(x), _stream(), _vp(rowmask)), "rg_seq_sum")
     return out
 
 
@@ -765,11 +775,13 @@ def cross_drop_scale(enc_ids, pad_value, H, drop_p, seed):
     return s
 
 
-def seq_wsum(x, s, B, L, H):
+def seq_wsum(x, s, B, L, H, rowmask=None):
+    """out[b, h] = sum_q s[b*L+q, h] * x[b, q]; rowmask [B*L] f32: rows with rowmask == 0 are not read (they may be unwritten)."""
     N = x.shape[-1]
     assert x.is_contiguous() and s.is_contiguous()
+    assert rowmask is None or (rowmask.dtype == torch.float32 and rowmask.numel() == B * L and rowmask.is_contiguous())
     out = torch.empty(B, H, N, device=x.device, dtype=x.dtype)
-    _check(lib().rg_seq_wsum(_vp(x), _vp(s), _vp(out), B, L, H, N, dt_of(x), _stream()), "rg_seq_wsum")
+    _check(lib().rg_seq_wsum(_vp(x), _vp(s), _vp(out), B, L, H, N, dt_of(x), _stream(), _vp(rowmask)), "rg_seq_wsum")
     return out
 
 
@@ -1507,6 +1519,34 @@ def attn_out_bwd(dy, y, rstd, gamma, beta, rowmask, dgamma, dbeta, Wot, live=Non
     return dz, dctx
 
 
+@_det_accum(dcgamma="g", dcbeta="g", dz_colsum="g", dgamma1="g", dbeta1="g")
+def attn_out_bwd_cross(dy2, y2, rstd_c, cgamma, cbeta, y1, rstd1, gamma1, beta1, rowmask, dcgamma, dcbeta, dgamma1, dbeta1, Wot,
+                       dz_colsum=None, live=None, w_packed=False):
+    """The decoder layer's attention tail, backwards, in one launch (rg_attn_out_bwd_cross): ln_bwd(dy2, y2, rstd_c, cgamma, cbeta,
+    rowmask, dcgamma, dcbeta, dz_colsum=...) -> dy1 followed by attn_out_bwd(dy1, y1, rstd1, gamma1, beta1, rowmask, dgamma1,
+    dbeta1, Wot) -> (dz, dctx).  Returns (dy1, dz, dctx); the five column sums are accumulated in place (fixed order, no
+    atomics).  With a live-tile list the padded tiles' rows of all three outputs stay unwritten."""
+    M, d = dy2.shape
+    P = d
+    assert dy2.is_contiguous() and y2.is_contiguous() and y1.is_contiguous() and dy2.dtype == y2.dtype == y1.dtype
+    assert y2.shape == dy2.shape and y1.shape == dy2.shape
+    dy1 = torch.empty_like(dy2)
+    dz = torch.empty_like(dy2)
+    dctx = torch.empty(M, P, device=dy2.device, dtype=dy2.dtype)
+    if POISON_UNWRITTEN and live is not None:
+        dy1.fill_(float("nan"))
+        dz.fill_(float("nan"))
+        dctx.fill_(float("nan"))
+    fn = lib().rg_attn_out_bwd_cross_workspace
+    fn.restype = ctypes.c_size_t
+    ws = _tn_workspace(dy2.device, int(fn(M)), "attn_out_cross_ln")
+    a = AttnOutBwdCrossArgs(_p(dy2), _p(y2), _p(rstd_c), _p(cgamma), _p(cbeta), _p(y1), _p(rstd1), _p(gamma1), _p(beta1), _p(rowmask),
+                            _p(Wot), _p(dy1), _p(dz), _p(dctx), _p(dcgamma), _p(dcbeta), _p(dz_colsum), _p(dgamma1), _p(dbeta1), _p(ws),
+                            M, d, P, 1 if w_packed else 0, _p(live))
+    _check(lib().rg_attn_out_bwd_cross(ctypes.byref(a), mt_of(dy2), _stream()), "rg_attn_out_bwd_cross")
+    return dy1, dz, dctx
+
+
 def ffn_bwd_data_supported(d, dff):
     return bool(lib().rg_ffn_bwd_data_supported(int(d), int(dff)))
 
@@ -1749,6 +1789,13 @@ def _work_attn_out_bwd(dy, y, rstd, *a, **k):
     return "attn_out_bwd_kernel", 2.0 * M * d * d, 4 * M * d * _esize(dy) + M * 4
 
 
+def _work_attn_out_bwd_cross(dy2, y2, rstd_c, *a, **k):
+    """Both LayerNorm backwards + dctx = dz . Wo: dy2, y2 and y1 rows read, dy1, dz and dctx rows written; rstd_c, rstd1 and the
+    row mask."""
+    M, d = dy2.shape
+    return "attn_out_bwd_cross_kernel", 2.0 * M * d * d, 6 * M * d * _esize(dy2) + 3 * M * 4
+
+
 def _work_ln_bwd(dy, y, rstd, *a, **k):
     M, N = dy.shape
     return "ln_bwd_kernel", 0.0, 3 * M * N * _esize(dy) + M * 4
@@ -1802,7 +1849,7 @@ def _work_shared_ce_dw(h, table_rows, labels, cand, mask, live, wc, lse, coef_po
             + (2 * n * d * _esize(h) if target_route else 0))
 
 
-_WORK = {"full_ce_fwd": _work_full_ce_fwd, "full_ce_dw": _work_full_ce_dw, "shared_ce_fwd": _work_shared_ce_fwd, "shared_ce_dw": _work_shared_ce_dw, "attn_out_bwd": _work_attn_out_bwd, "ln_bwd": _work_ln_bwd, "gemm_tn_layer": _work_gemm_tn_layer, "item_loss_scatter_binned": _work_item_loss_scatter, "attn_lastq_x_fwd": _work_lastq_x_fwd, "attn_lastq_x_bwd": _work_lastq_x_bwd, "item_loss_train": _work_item_loss_train,
+_WORK = {"full_ce_fwd": _work_full_ce_fwd, "full_ce_dw": _work_full_ce_dw, "shared_ce_fwd": _work_shared_ce_fwd, "shared_ce_dw": _work_shared_ce_dw, "attn_out_bwd": _work_attn_out_bwd, "attn_out_bwd_cross": _work_attn_out_bwd_cross, "ln_bwd": _work_ln_bwd, "gemm_tn_layer": _work_gemm_tn_layer, "item_loss_scatter_binned": _work_item_loss_scatter, "attn_lastq_x_fwd": _work_lastq_x_fwd, "attn_lastq_x_bwd": _work_lastq_x_bwd, "item_loss_train": _work_item_loss_train,
          "ffn_bwd_data": _work_ffn_bwd, "attn_fwd_x": _work_attn_fwd_x, "post_attn_fwd": _work_post_attn, "gemm_nt": _work_gemm_nt, "gemm_tn": _work_gemm_tn, "attn_fwd": _work_attn_fwd, "attn_bwd": _work_attn_bwd,
          "embed_pe_fwd": _work_embed_fwd, "item_loss_fwd": _work_item_loss, "item_loss_bwd": _work_item_loss}
 _PLAIN = ["dropout_", "cross_rows", "adam_multi", "adam_multi_dev", "adam_multi_dev2", "grad_sqnorm_multi", "disc_rows", "item_loss_bwd_binned", "embed_scatter_bwd", "bcast_add_ln", "seq_sum", "colsum", "outer_posmask", "interpolate",

@@ -651,6 +651,7 @@ QKV_HEAD_MAJOR_TRAIN = True    # ... in training passes too (the backward reads 
 EMBED_SCATTER_BINNED = True  # rg_embed_scatter_bwd_binned at >= 65536 positions
 FUSE_ITEM_LOSS_TRAIN = True   # rg_item_loss_train: loss, coefficients and dh from one gather of the 1+k rows
 FUSE_ATTN_OUT_BWD = True     # rg_attn_out_bwd (LayerNorm-1 backward + dctx product) for d_model == P == 128
+FUSE_ATTN_OUT_BWD_CROSS = True   # ... decoder layers: with the cross-attention LayerNorm backward in front (rg_attn_out_bwd_cross)
 LASTQ_FROM_X = True   # rg_attn_lastq_x_* / _xf_*: the last layer's single-query attention straight from x (no K / V)
 LASTQ_FOLD_PREFIX = True
 ATTN_RESIDENT_MAX_L = 416      # rg_attn_fwd / rg_attn_bwd keep a head's key range on chip up to here; 416 < L <= 2048: the streaming form
@@ -754,6 +755,19 @@ def _attn_block_bwd(dy, x2, y, saved, B, L, key_ids, pad_value, causal, H, prm, 
         dz = hip.ln_bwd(dy, y, rstd, g.detach(), be.detach(), rowmask, dg, dbe, live=live)
         hip.gemm_tn(dz, ctx_.view(B * L, P), dWo, dbo, live=live if live is not None else _live_tn(rowmask, dz.shape[0], P, d))
         dctx = hip.gemm_nt(dz, shadow(Wo, transpose=True), live=live, skip_dead_fill=True)   # attn_bwd: rowmask-driven
+    dx, gqkv = _attn_block_bwd_qkv(dz, dctx, live, x2, saved, B, L, key_ids, pad_value, causal, H, prm, drop_p, seed, rowmask, x_masked)
+    return dx, gqkv + (rWo, rbo, rg, rbe)
+
+
+def _attn_block_bwd_qkv(dz, dctx, live, x2, saved, B, L, key_ids, pad_value, causal, H, prm, drop_p=0.0, seed=0, rowmask=None,
+                        x_masked=False):
+    """The rest of the attention block's backward, from dz (the gradient at the LayerNorm input: residual path) and dctx, both of
+    which may have the rows of the tiles missing from `live` unwritten: attention, Q / K / V weight gradients, dx.  Returns dx and
+    what autograd gets for Wq, bq, Wk, bk, Wv, bv."""
+    Wq, bq, Wk, bk, Wv, bv = prm[:6]
+    qkv, ctx_, lse, _ = saved
+    d = x2.shape[1]
+    P = prm[6].shape[1]
     # the forward's decision (same inputs; x_masked == 2: it was the fused block's forward): were the padded tiles' rows of
     # qkv left unwritten?
     sub = (QKV_BIAS_ROWS_IN_ATTENTION and x_masked == 2 and _unwritten_qkv_ok() and L <= ATTN_RESIDENT_MAX_L
@@ -775,7 +789,7 @@ def _attn_block_bwd(dy, x2, y, saved, B, L, key_ids, pad_value, causal, H, prm, 
         dx = hip.gemm_nt(dqkv2[:, 384:], Wt[:, 384:], epilogue=hip.EPI_ADD, aux=dx, out=dx, live=live)
     else:
         dx = hip.gemm_nt(dqkv2, Wt, epilogue=hip.EPI_ADD, aux=dz, live=live)
-    return dx, (rW[0], rb[0], rW[1], rb[1], rW[2], rb[2], rWo, rbo, rg, rbe)
+    return dx, (rW[0], rb[0], rW[1], rb[1], rW[2], rb[2])
 
 
 def _ffn_block_fwd(y, rowmask, W1, b1, W2, b2, g, be, drop_p=0.0, seed_h1=0, seed_out=0):
@@ -1126,14 +1140,27 @@ class DecoderLayerFn(_Fn):
             (dcWo, rcWo), (dcbo, rcbo) = _gt(cWo), _gt(cbo)
             # residual: dz == dy1; under dropout the cross-attention output bias gradient is the column sum of dy1, which
             # the same kernel accumulates
-            dy1 = hip.ln_bwd(dy2, y2, rstd_c, cg.detach(), cbe.detach(), rowmask, dcg, dcbe,
-                             dz_colsum=dcbo if s_cross is not None else None)
+            Wo, bo, g1, be1 = ctx.prm[6:10]
+            cross = FUSE_ATTN_OUT_BWD_CROSS and FUSE_ATTN_OUT_BWD and d == 128 and Wo.shape[1] == 128
+            if cross:
+                # ... and the self-attention tail's LayerNorm backward + dctx product behind it, on the same staged rows: dy1 is
+                # written once (live tiles only) and read back only by the per-sequence sum below, which skips the padded rows
+                (dg1, rg1), (dbe1, rbe1) = _gt(g1), _gt(be1)
+                live = _live(rowmask, B * L)
+                dy1, dz, dctx = hip.attn_out_bwd_cross(dy2, y2, rstd_c, cg.detach(), cbe.detach(), y1, rstd1, g1.detach(), be1.detach(),
+                                                       rowmask, dcg, dcbe, dg1, dbe1, shadow(Wo, transpose=True, pack=True, split=True),
+                                                       dz_colsum=dcbo if s_cross is not None else None, live=live, w_packed=True)
+                rm = rowmask
+            else:
+                dy1 = hip.ln_bwd(dy2, y2, rstd_c, cg.detach(), cbe.detach(), rowmask, dcg, dcbe,
+                                 dz_colsum=dcbo if s_cross is not None else None)
+                rm = None
             if s_cross is None:
-                do = hip.seq_sum(dy1, B, L)                                                  # [B, d] tier dtype
+                do = hip.seq_sum(dy1, B, L, rowmask=rm)                                      # [B, d] tier dtype
                 hip.gemm_tn(do, c, dcWo, dcbo)
                 dc = hip.gemm_nt(do, shadow(cWo, transpose=True))                            # [B, P]
             else:
-                doh = hip.seq_wsum(dy1, s_cross, B, L, H)                                    # [B, H, d]
+                doh = hip.seq_wsum(dy1, s_cross, B, L, H, rowmask=rm)                        # [B, H, d]
                 # all heads at once (see the forward): dWo[:, block h] += doh[:, h, :]^T c[:, block h] is one TN product
                 # against the head-masked stack of c; dc's block h is the diagonal block of doh[:, h, :] @ Wo
                 eye = _head_eye(H, c)
@@ -1145,8 +1172,15 @@ class DecoderLayerFn(_Fn):
             (dcWv, rcWv), (dcbv, rcbv) = _gt(cWv), _gt(cbv)
             hip.gemm_tn(dc, u, dcWv, dcbv)
             du = hip.gemm_nt(dc, shadow(cWv, transpose=True))                                # [B, d]
-            dx, ga = _attn_block_bwd(dy1, x2, y1, (qkv, ctx_, lse, rstd1), B, L, key_ids, 0, True, H,
-                                     ctx.prm[:10], drop_p, seeds[0], rowmask, xm)
+            if cross:
+                (dWo, rWo), (dbo, rbo) = _gt(Wo), _gt(bo)
+                _tn(dz, ctx_.view(B * L, Wo.shape[1]), dWo, dbo, live=live)
+                dx, ga = _attn_block_bwd_qkv(dz, dctx, live, x2, (qkv, ctx_, lse, rstd1), B, L, key_ids, 0, True, H,
+                                             ctx.prm[:10], drop_p, seeds[0], rowmask, xm)
+                ga = ga + (rWo, rbo, rg1, rbe1)
+            else:
+                dx, ga = _attn_block_bwd(dy1, x2, y1, (qkv, ctx_, lse, rstd1), B, L, key_ids, 0, True, H,
+                                         ctx.prm[:10], drop_p, seeds[0], rowmask, xm)
         return ((dx.view(B, L, d), du.to(ctx.u_dtype), None, None, None, None, None) + ga + (rcWv, rcbv, rcWo, rcbo, rcg, rcbe) + gf)
 
 
