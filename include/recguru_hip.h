@@ -250,6 +250,18 @@ size_t rg_embed_scatter_binned_workspace(long long ntok, int d, long long table_
 int rg_embed_scatter_bwd_binned(const void* dx, const int64_t* ids, const float* mask, float* dE, long long ntok, int d,
                                 long long table_rows, long long skip_row, float drop_p, unsigned long long seed,
                                 void* workspace, size_t workspace_bytes, int dtype, void* stream);
+/* Gradient of a LEARNED positional table (PositionalEncodingM of transformer.py:327-342, pos_train=True):
+ *     dP[l, e] += sum_b dx[b, l, e] * mask[b*L + l] * keep(seed, drop_p, (unsigned)(b*L + l) * (unsigned)d + e)      for l < L
+ * with the forward's 32-bit wrapping index and mask (keep = 0 or the f32 1/(1-p)).  dx [B, L, d] dtype (RG_BF16 or RG_F32), contiguous;
+ * dP [>= L, d] f32, accumulated into, rows >= L untouched; a position with mask == 0 contributes nothing and its dx row is not read.
+ * Any B, L >= 1 with B * L < 2^31 and d % 8 == 0 (d 64 / 128 / 256 specialised).  Two launches, no atomics: per-slice partial rows
+ * into workspace [slices][L][d] f32, then the slices added in ascending order; the slice count is a function of (B, L, d) only, so equal
+ * inputs give equal bits on every run and in both libraries.  rg_pos_grad_workspace: bytes of scratch = slices * L * d * 4 (0: shape not
+ * supported).  A missing buffer, a bad dtype or a workspace that is too small: RG_ERR_INVALID; an unsupported shape:
+ * RG_ERR_UNSUPPORTED; both before any launch. */
+size_t rg_pos_grad_workspace(int B, int L, int d);
+int rg_pos_grad(const void* dx, const float* mask, float* dP, int B, int L, int d, float drop_p, unsigned long long seed,
+                void* workspace, size_t workspace_bytes, int dtype, void* stream);
 /* drop_p / seed: nn.Dropout of PositionalEncoding.forward (transformer.py:106); the mask is a stateless
  * hash of (seed, element index), regenerated by the backward.  drop_p = 0 disables it. */
 

@@ -236,7 +236,7 @@ def main(args_t, device_t, train_loader_ae, train_loader_re, eval_loader, loader
     if s2b(sas_):
         raise NotImplementedError("the SASRec baseline (--sas True) is out of scope")
     MyModel = models.MyRec(device_t, args_t, wf=item_freq, dec_rec=s2b(shared), fix_enc=s2b(fix_enc), sas=False,
-                           pos_train=False).to(torch.float32).to(device_t)
+                           pos_train=bool(getattr(args_t, "pos_train", False))).to(torch.float32).to(device_t)
     opt = blocks.ScheduledOptim(Adam(MyModel.parameters(), betas=(0.9, 0.99), eps=1e-09, **adam_options(args_t)), 1.0, args_t.d_model,
                                 args_t.n_warmup_steps)
     pre, _ = train(MyModel, opt, args_t.training_steps, [train_loader_ae, train_loader_ae], args_t, device_t,

@@ -72,6 +72,31 @@ class PositionalEncoding(nn.Module):
         return _rate(self.dropout_rate) if self.training else 0.0
 
 
+class PositionalEncodingM(nn.Module):
+    """Learned positions, transformer.py:327-342: an nn.Embedding(max_len, d_model) under the reference's key 'pos_emb.weight'
+    (N(0, 1) default initialisation), no 'pe' buffer.  The embedding kernels read the weight as the positional table; its gradient
+    comes from rg_pos_grad (ops.EmbedPE.backward)."""
+
+    def __init__(self, d_model, dropout, max_len=5000, device=None):
+        super(PositionalEncodingM, self).__init__()
+        self.dropout_rate = dropout
+        self.device = device
+        self.pos_emb = nn.Embedding(max_len, d_model)
+
+    def table(self):
+        return self.pos_emb.weight
+
+    def drop_p(self):
+        return _rate(self.dropout_rate) if self.training else 0.0
+
+
+def check_positions(pos, L):
+    """A batch longer than the positional table has no rows to read: refuse it before any launch."""
+    rows = pos.table().shape[0]
+    if L > rows:
+        raise ValueError("sequence length %d exceeds the positional table's %d rows (enc_maxlen)" % (L, rows))
+
+
 class MultiHeadAttention(nn.Module):
     def __init__(self, d_model, d_k, d_v, n_heads, device, dropout_rate=None):
         super(MultiHeadAttention, self).__init__()

@@ -45,6 +45,7 @@ class get_param(object):
         self.rs_d_model, self.rs_num_blocks, self.rs_d_ff = args.d_model, self.num_blocks, args.d_ff
         self.n_negs = args.n_negs
         self.shared_negs = int(_opt(args, "shared_negs", 0))       # > 0: one shared candidate list per reconstruction batch
+        self.pos_train = bool(_opt(args, "pos_train", False))      # True: learned positional table (blocks.PositionalEncodingM) instead of the sinusoid
         # optimizer options (recguru_amd/optim.py), all neutral by default: the reference configures none of them
         self.weight_decay = float(_opt(args, "weight_decay", 0.0))
         self.decoupled_wd = bool(_opt(args, "decoupled_wd", False))       # True: AdamW's p *= 1 - lr * wd; False: Adam's g += wd * p

@@ -316,6 +316,89 @@ __global__ __launch_bounds__(EW_BLOCK) void embed_scatter_bwd_kernel(const T* __
   }
 }
 
+// Gradient of a LEARNED positional table (blocks.PositionalEncodingM; rg_pos_grad):
+//   dP[l,e] += sum_b dx[b,l,e] * mask[b*L+l] * keep(seed, (unsigned)(b*L+l) * (unsigned)d + e)
+// -- the index expression of embed_pe_fwd_pos_kernel / embed_scatter_bwd_kernel, so the mask is the forward's.  Two launches, no atomics:
+// (1) position-major like the forward: a wave owns RPW consecutive positions (D / 8 lanes per row, 16-byte loads in bf16) and ONE slice
+// [sl * bs, (sl + 1) * bs) of the batch, which it sums in registers in ascending b, U rows in flight, and writes to part[sl][L][d];
+// (2) one lane per element adds the slices in ascending order onto dP.  The slice count depends on (B, L, d) only (pos_grad_slices), so the
+// order of every addition is fixed: equal inputs give equal bits, in both libraries.  The row of a masked position is NOT read (its lanes
+// load row 0 of dx instead, one hot line set, and the value is discarded by a select, never multiplied: a NaN there stays there); a group
+// of U positions that are padding in every lane of the wave (left padding) issues no row loads at all.
+// D == 0: any d % 8 == 0, one lane per (slice, position, 8 columns); same two stages, same order.
+#define PG_UNROLL 4           // rows in flight per lane (8: 41.5 against 39.7 us at the bench shape, profiles/pos_train/ab.txt)
+#define PG_WG_PER_CU 4        // workgroups per CU the launch aims at: more = more loads in flight, and as many more partial rows (2: 56 us, 8: 42 us)
+#define PG_MIN_SLICE 16       // sequences per slice at least (a multiple of PG_UNROLL): a partial row costs a write and a read of 4 d bytes
+template <typename T, int D, int U>
+__global__ __launch_bounds__(EW_BLOCK) void pos_grad_part_kernel(const T* __restrict__ dx, const float* __restrict__ mask,
+                                                                float* __restrict__ part, int B, int L, int d, int bs, DropCfg drop) {
+  int pos, c8, sl;
+  if constexpr (D > 0) {
+    constexpr int LPR = D / 8, RPW = 64 / LPR;           // lanes per row, positions per wave
+    const int lane = threadIdx.x & 63;
+    const int wave = (int)((blockIdx.x * EW_BLOCK + threadIdx.x) >> 6);
+    const int npb = (L + RPW - 1) / RPW;
+    sl = wave / npb;
+    pos = (wave % npb) * RPW + lane / LPR;
+    c8 = (lane % LPR) * 8;
+  } else {
+    const int cpr = d >> 3;
+    const int i = (int)(blockIdx.x * EW_BLOCK + threadIdx.x), t = i / cpr;
+    c8 = (i - t * cpr) * 8;
+    sl = t / L;
+    pos = t - sl * L;
+  }
+  const int dd = D > 0 ? D : d;
+  const int b0 = sl * bs;
+  if (b0 >= B) return;                                   // (the grid's tail: no such slice)
+  const int b1 = min(B, b0 + bs);
+  const bool inr = pos < L;
+  const int posc = inr ? pos : L - 1;
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+#pragma unroll 1
+  for (int b = b0; b < b1; b += U) {
+    float m[U];
+    bool anyl = false;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const float mm = mask[min(b + u, b1 - 1) * L + posc];
+      m[u] = (inr && b + u < b1) ? mm : 0.f;
+      anyl = anyl || m[u] != 0.f;
+    }
+    if (__ballot(anyl) == 0ull) continue;
+    float v[U][8];
+#pragma unroll
+    for (int u = 0; u < U; ++u) load8(v[u], dx + (m[u] != 0.f ? (size_t)((b + u) * L + pos) * dd : (size_t)0) + c8);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (m[u] != 0.f) {
+        const int tok = (b + u) * L + pos;
+        if (drop.thresh) {
+          float k8[8];
+          rg_keep8(drop, (unsigned int)tok * (unsigned int)dd + (unsigned int)c8, k8);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[j] += v[u][j] * m[u] * k8[j];
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[j] += v[u][j] * m[u];
+        }
+      }
+    }
+  }
+  if (inr) store8(part + ((size_t)sl * L + pos) * dd + c8, acc);
+}
+
+__global__ __launch_bounds__(EW_BLOCK) void pos_grad_sum_kernel(const float* __restrict__ part, float* __restrict__ dP, int n, int nsl) {
+  const int i = (int)(blockIdx.x * EW_BLOCK + threadIdx.x);
+  if (i >= n) return;
+  float s = 0.f;
+#pragma unroll 8
+  for (int k = 0; k < nsl; ++k) s += part[(size_t)k * n + i];
+  dP[i] += s;
+}
+
 // ------------------------------------------------------------------------------------------------
 // LayerNorm backward from the saved OUTPUT: xhat = (y - beta) / gamma, rstd saved by the forward.
 //   g = dy * rowmask * gamma ; dz = rstd * (g - mean(g) - xhat * mean(g * xhat))
@@ -1409,6 +1492,61 @@ extern "C" int rg_embed_scatter_bwd(const void* dx, const int64_t* ids, const fl
   } while (0)
   DISPATCH_T(dtype, RG_ES_T(__bf16), RG_ES_T(float),
              "embed_scatter_bwd")
+}
+
+// Slices of the batch for rg_pos_grad (0: shape not supported) and the sequences per slice: a function of (B, L, d) ONLY -- the order of the
+// additions, and so the bits of the result, follow from it.  Waves = position blocks x slices, aimed at ~ 4 workgroups (16 waves) per CU.
+static int pos_grad_slices(int B, int L, int d, int* bs_out) {
+  if (B < 1 || L < 1 || d < 8 || (d & 7) || (long long)B * L >= (1ll << 31) || (long long)L * d >= (1ll << 31)) return 0;
+  const bool spec = d == 64 || d == 128 || d == 256;
+  const long long rpw = spec ? 64 / (d / 8) : 1, npb = (L + rpw - 1) / rpw;
+  const long long cap = 256LL * PG_WG_PER_CU * (EW_BLOCK / 64);
+  long long chunks = (cap + npb - 1) / npb;
+  if (chunks > B) chunks = B;
+  long long bs = (B + chunks - 1) / chunks;
+  if (bs < PG_MIN_SLICE) bs = PG_MIN_SLICE;
+  const long long nsl = (B + bs - 1) / bs;
+  // (generic form: one lane per (slice, position, 8 columns), indexed in 32 bits)
+  if (!spec && nsl * L * (d >> 3) >= (1ll << 31) - EW_BLOCK) return 0;
+  if (spec && nsl * npb * 64 >= (1ll << 31) - EW_BLOCK) return 0;
+  if (bs_out) *bs_out = (int)bs;
+  return (int)nsl;
+}
+
+extern "C" size_t rg_pos_grad_workspace(int B, int L, int d) {
+  return (size_t)pos_grad_slices(B, L, d, nullptr) * (size_t)L * (size_t)d * sizeof(float);
+}
+
+extern "C" int rg_pos_grad(const void* dx, const float* mask, float* dP, int B, int L, int d, float drop_p, unsigned long long seed,
+                           void* workspace, size_t workspace_bytes, int dtype, void* stream) {
+  if (!dx || !mask || !dP || !workspace) return rg_set_error_msg(RG_ERR_INVALID, "pos_grad: dx, mask, dP and workspace are required");
+  if (dtype != RG_BF16 && dtype != RG_F32) return rg_set_error_msg(RG_ERR_INVALID, "pos_grad: bad dtype");
+  int bs = 0;
+  const int nsl = pos_grad_slices(B, L, d, &bs);
+  if (nsl == 0) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "pos_grad: needs B, L >= 1, d % 8 == 0, B * L < 2^31 (rg_pos_grad_workspace() == 0)");
+  if (workspace_bytes < (size_t)nsl * L * d * sizeof(float)) return rg_set_error_msg(RG_ERR_INVALID, "pos_grad: workspace smaller than rg_pos_grad_workspace()");
+  const DropCfg drop = make_drop(drop_p, seed);
+  hipStream_t s = (hipStream_t)stream;
+  float* part = (float*)workspace;
+  const bool spec = d == 64 || d == 128 || d == 256;
+  const long long threads = spec ? (long long)nsl * ((L + 64 / (d / 8) - 1) / (64 / (d / 8))) * 64 : (long long)nsl * L * (d >> 3);
+  const int grid = (int)((threads + EW_BLOCK - 1) / EW_BLOCK);
+#define RG_PG(T, D) hipLaunchKernelGGL((pos_grad_part_kernel<T, D, PG_UNROLL>), dim3(grid), dim3(EW_BLOCK), 0, s, (const T*)dx, mask, part, B, L, d, bs, drop)
+#define RG_PG_T(T)                    \
+  do {                                \
+    if (d == 64) RG_PG(T, 64);        \
+    else if (d == 128) RG_PG(T, 128); \
+    else if (d == 256) RG_PG(T, 256); \
+    else RG_PG(T, 0);                 \
+  } while (0)
+  if (dtype == RG_BF16) RG_PG_T(__bf16); else RG_PG_T(float);
+#undef RG_PG_T
+#undef RG_PG
+  RG_CHECK_LAUNCH();
+  const int n = L * d;
+  hipLaunchKernelGGL(pos_grad_sum_kernel, dim3((n + EW_BLOCK - 1) / EW_BLOCK), dim3(EW_BLOCK), 0, s, part, dP, n, nsl);
+  RG_CHECK_LAUNCH();
+  return 0;
 }
 
 template <typename T>

@@ -111,7 +111,8 @@ SYMBOLS = ["rg_last_error", "rg_version", "rg_gemm_nt", "rg_gemm_tn", "rg_attn_f
            "rg_full_ce_supported", "rg_full_ce_fwd", "rg_full_ce_dw",
            "rg_shared_ce_supported", "rg_shared_ce_bwd_workspace", "rg_shared_ce_fwd", "rg_shared_ce_bwd",
            "rg_topk_workspace", "rg_topk_scores", "rg_topk_list_workspace", "rg_topk_list",
-           "rg_grad_sqnorm_multi", "rg_adam_multi_dev2"]
+           "rg_grad_sqnorm_multi", "rg_adam_multi_dev2",
+           "rg_pos_grad_workspace", "rg_pos_grad"]
 LOSS_SAMPLED_CE, LOSS_BPR, LOSS_BPR_SAS = 0, 1, 2
 c_ll = ctypes.c_longlong
 
@@ -633,6 +634,35 @@ def embed_scatter_bwd_binned(dx, ids, mask, dE, skip_row=-1, drop_p=0.0, seed=0)
                                              c_ll(skip_row), c_f(drop_p), c_u64(seed), _vp(ws), ctypes.c_size_t(need),
                                              dt_of(dx), _stream()), "rg_embed_scatter_bwd_binned")
     return dE
+
+
+def pos_grad_workspace(B, L, d):
+    """Bytes of scratch rg_pos_grad needs = slices * L * d * 4 (0: shape not supported)."""
+    fn = lib().rg_pos_grad_workspace
+    fn.restype = ctypes.c_size_t
+    return int(fn(int(B), int(L), int(d)))
+
+
+_POS_WS = {}
+
+
+def pos_grad(dx, mask, dP, B, L, drop_p=0.0, seed=0):
+    """dP[l] += sum_b dx[b, l] * mask[b, l] * keep(seed, idx): the gradient of a learned positional table (rg_pos_grad).  Two launches
+    with a fixed summation order and no atomics, so no deterministic-arena wrapping: the same bits in both libraries.  The scratch is
+    cached per device like _BIN_WS: it is consumed inside the call that fills it."""
+    d = dx.shape[-1]
+    assert dx.is_contiguous() and dx.numel() == B * L * d and mask.dtype == torch.float32 and mask.is_contiguous() and mask.numel() == B * L
+    assert dP.dtype == torch.float32 and dP.is_contiguous() and dP.dim() == 2 and dP.shape[1] == d and dP.shape[0] >= L
+    need = pos_grad_workspace(B, L, d)
+    if not need:
+        raise RuntimeError("pos_grad: unsupported shape (B=%d, L=%d, d=%d)" % (B, L, d))
+    ws = _POS_WS.get(dx.device)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=dx.device, dtype=torch.uint8)
+        _POS_WS[dx.device] = ws
+    _check(lib().rg_pos_grad(_vp(dx), _vp(mask), _vp(dP), int(B), int(L), int(d), c_f(drop_p), c_u64(seed), _vp(ws),
+                             ctypes.c_size_t(need), dt_of(dx), _stream()), "rg_pos_grad")
+    return dP
 
 
 @_det_accum(dgamma="g", dbeta="g", dz_colsum="g")

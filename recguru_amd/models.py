@@ -142,7 +142,10 @@ class Discriminator(nn.Module):
 
 
 class MyAuto4Rec_c(nn.Module):
-    def __init__(self, device, param, wf=None, dec_share=False, dec_rec=False, enc_share=True):
+    def __init__(self, device, param, wf=None, dec_share=False, dec_rec=False, enc_share=True, pos_train=False):
+        """pos_train=True: pos_emb_a / pos_emb_b are learned tables (blocks.PositionalEncodingM, max_len = param.enc_maxlen; state keys
+        pos_emb_{a|b}.pos_emb.weight, no 'pe' buffers).  The reference's cross model has no such option (AutoEnc4Rec_cross.py:17): it is
+        this project's extension, off by default."""
         super(MyAuto4Rec_c, self).__init__()
         self.param = param
         self.device = device
@@ -161,10 +164,14 @@ class MyAuto4Rec_c(nn.Module):
                        device=device, dropout=param.dropout_rate)
         # construction order follows the reference so that default initialisation under a given
         # torch seed produces the same state_dict
+        def positions():
+            if pos_train:
+                return blocks.PositionalEncodingM(param.d_model, param.dropout_rate, max_len=param.enc_maxlen, device=device)
+            return blocks.PositionalEncoding(param.d_model, param.dropout_rate)
         self.src_emb_a = nn.Embedding(param.vocab_size_a + 1, param.d_model)
-        self.pos_emb_a = blocks.PositionalEncoding(param.d_model, param.dropout_rate)
+        self.pos_emb_a = positions()
         self.src_emb_b = nn.Embedding(param.vocab_size_b + 1, param.d_model)
-        self.pos_emb_b = blocks.PositionalEncoding(param.d_model, param.dropout_rate)
+        self.pos_emb_b = positions()
         if enc_share:
             self.encoder = stack(blocks.EncoderM)
         else:
@@ -189,6 +196,7 @@ class MyAuto4Rec_c(nn.Module):
 
     def _embed(self, ids, domain, mask):
         emb, pos = self._emb(domain)
+        blocks.check_positions(pos, ids.shape[1])
         return ops.embed_pe(emb.weight, pos.table(), ids, mask, drop_p=pos.drop_p())
 
     def _encoder(self, domain):
@@ -255,8 +263,6 @@ class MyAuto4Rec(nn.Module):
     def __init__(self, vocab_size, d_model, pad_index, d_ff, d_k, d_v, n_heads, n_layers, device, param,
                  wf=None, pos_train=False):
         super(MyAuto4Rec, self).__init__()
-        if pos_train:
-            raise NotImplementedError("trainable positional encoding (pos_train) is outside the hot path")
         self.pad_index = pad_index
         self.param = param
         self.device = device
@@ -266,7 +272,10 @@ class MyAuto4Rec(nn.Module):
         else:
             self.weights = None
         self.src_emb = nn.Embedding(vocab_size + 1, d_model, padding_idx=pad_index)
-        self.pos_emb = blocks.PositionalEncoding(d_model, param.dropout_rate)
+        if pos_train:       # learned positions (AutoEnc4Rec.py:155-157), in the reference's construction position
+            self.pos_emb = blocks.PositionalEncodingM(d_model, param.dropout_rate, max_len=param.enc_maxlen, device=device)
+        else:
+            self.pos_emb = blocks.PositionalEncoding(d_model, param.dropout_rate)
         self.encoder = blocks.EncoderM(d_model=d_model, d_ff=d_ff, d_k=d_k, d_v=d_v, n_heads=n_heads,
                                        n_layers=n_layers, pad_index=pad_index, device=device,
                                        dropout=param.dropout_rate)
@@ -275,6 +284,7 @@ class MyAuto4Rec(nn.Module):
                                        dropout=param.dropout_rate)
 
     def _embed(self, ids, mask):
+        blocks.check_positions(self.pos_emb, ids.shape[1])
         # padding_idx row receives no gradient (AutoEnc4Rec.py:153)
         return ops.embed_pe(self.src_emb.weight, self.pos_emb.table(), ids, mask, skip_row=self.pad_index,
                             drop_p=self.pos_emb.drop_p())

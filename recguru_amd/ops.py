@@ -555,7 +555,7 @@ class EmbedPE(_Fn):
         else:
             out = hip.embed_pe_fwd(shadow(table), pe, ids, mask, L, drop_p, seed)
         ctx.save_for_backward(ids, mask)
-        ctx.table = table
+        ctx.table, ctx.pe = table, pe
         ctx.meta = (skip_row, drop_p, seed)
         return out.view(B, L, -1)
 
@@ -569,7 +569,13 @@ class EmbedPE(_Fn):
         binned = (EMBED_SCATTER_BINNED and dx2.shape[0] >= 65536
                   and hip.embed_scatter_binned_supported(dx2.shape[0], dx2.shape[1], dE.shape[0]))
         (hip.embed_scatter_bwd_binned if binned else hip.embed_scatter_bwd)(dx2, ids, mask, dE, skip_row, drop_p, seed)
-        return ret, None, None, None, None, None
+        ret_pe = None
+        if ctx.needs_input_grad[1]:
+            # a learned positional table (blocks.PositionalEncodingM): the same rows, mask and dropout seed summed over the batch.  The fixed
+            # sinusoid buffer requires no gradient and launches nothing here.
+            dP, ret_pe = _gt(ctx.pe)
+            hip.pos_grad(dx2, mask, dP, ids.shape[0], ids.shape[1], drop_p, seed)
+        return ret, ret_pe, None, None, None, None
 
 
 def embed_pe(table, pe, ids, mask, skip_row=-1, drop_p=0.0):

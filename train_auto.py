@@ -50,6 +50,8 @@ def parse():
     p.add_argument("--shared_negs", type=int, default=0,
                    help="pre-training loader only: draw this many candidates ONCE per batch and share them among all positions "
                         "(DESIGN.md 6e) instead of n_negs private negatives per position; 0 = off")
+    p.add_argument("--pos_train", type=lambda v: v == "True", default=False,
+                   help="True: learned positional table of enc_maxlen rows (the reference's pos_train) instead of the fixed sinusoid")
     p.add_argument("--weight_decay", type=float, default=0.0, help="weight decay of both optimizers (recguru_amd/optim.py); 0 = off, as the reference")
     p.add_argument("--decoupled_wd", type=lambda v: v == "True", default=False,
                    help="True: AdamW's decoupled decay (p *= 1 - lr * wd); False: torch.optim.Adam's (g += wd * p)")

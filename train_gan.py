@@ -60,6 +60,9 @@ def parse():
     p.add_argument("--shared_negs", type=int, default=0,
                    help="reconstruction loaders only: draw this many candidates ONCE per batch and share them among all positions "
                         "(sampled softmax over one candidate list, DESIGN.md 6e) instead of n_negs private negatives per position; 0 = off")
+    p.add_argument("--pos_train", type=str2bool_par, default=False,
+                   help="True: learned positional tables of enc_maxlen rows for both domains instead of the fixed sinusoid "
+                        "(this project's extension of the cross model)")
     p.add_argument("--weight_decay", type=float, default=0.0,
                    help="weight decay of the reconstruction / recommender optimizers (recguru_amd/optim.py); 0 = off, as the reference")
     p.add_argument("--decoupled_wd", type=str2bool_par, default=False,
@@ -142,7 +145,7 @@ def main():
         test_loaders = Dataloader.eval_loader_gen(files[t], param, t, device, 0, 1, wf=freq)        # unsharded, see above
     torch.manual_seed(1)                                           # gan_training.py:20 (same initial weights on every rank)
     enc_model = Model.MyAuto4Rec_c(device, param, wf=None, enc_share=args.enc_share != "False",
-                                   dec_rec=False).to(torch.float32).to(device)
+                                   dec_rec=False, pos_train=param.pos_train).to(torch.float32).to(device)
     opt_rec = all_module.ScheduledOptim(Adam(enc_model.parameters(), betas=(0.9, 0.98), eps=1e-09, **adam_options(param)),
                                         1.0, param.d_model, param.n_warmup_steps)
     # the W-GAN pair takes no decay and no clip (the gradient penalty sets that balance), only the non-finite skip
