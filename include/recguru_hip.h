@@ -873,6 +873,41 @@ int rg_cross_drop_scale(const int64_t* enc_ids, int64_t pad_value, float* s, int
 /* rg_seq_wsum rowmask [B*L] f32 or NULL: as for rg_seq_sum (L more floats of LDS). */
 int rg_seq_wsum(const void* x, const float* s, void* out, int B, int L, int H, int N, int dtype, void* stream, const float* rowmask);
 
+/* ---- attention maps on request ---------------------------------------------------------------------
+ * What the reference's stacks return beside their outputs (EncoderM.forward: enc_self_attns, DecoderM.forward: dec_self_attns and
+ * dec_enc_attns, transformer.py:587-599 / :520-549; each [B, n_layers, H, L, L] f32).  The training kernels keep the
+ * probabilities in registers; these entry points write them for inspection.  No gradient, no dropout.
+ *
+ * rg_attn_probs: softmax(mask(Q K^T * scale)) of every (sequence, head), ScaledDotProductAttention (transformer.py:119-125),
+ * under the masking contract of rg_attn_args: masked(q, key) = key_ids[b, key] == pad_value || (causal && key > q); masked scores
+ * are REPLACED by -1e9 (quirk Q3); softmax in f32 over all L keys.  1 <= L <= 2048, dk == 32; dtype RG_BF16 / RG_F32 / RG_X3
+ * (the storage type of qkv: bf16 / f32 / f32).  One streaming kernel for every length, two sweeps over the keys, no atomics,
+ * every element written by exactly one lane.  Exact: a masked key of a row with a visible key is +0.0; a row with exactly one
+ * visible key is 1.0 there; a row without a visible key (every row of an all-padding sequence, the padded prefix rows of a
+ * left-padded causal one) is float32(1) / float32(L) in ALL L columns, future keys included; a (b, h) map has the same bits
+ * whatever B and the position of b in the batch.
+ * RG_ERR_UNSUPPORTED: dk != 32, L > 2048, bad dtype; RG_ERR_INVALID: a null pointer, L < 1, b_stride < H*L*L -- before any launch. */
+typedef struct {
+  const void* qkv;            /* [B, L, 3*H*32] token-major Q | K | V in the tier's storage type; V is not read */
+  const int64_t* key_ids; int64_t pad_value; int causal;
+  float* probs;               /* element (b, h, q, key) at probs[b*b_stride + (h*L + q)*L + key]; every element written */
+  long long b_stride;         /* elements between consecutive b: H*L*L for a [B,H,L,L] tensor, N*H*L*L to write layer l of a
+                                 [B,N,H,L,L] tensor in place (probs then points at [0, l]) */
+  int B, L, H, dk; float scale;
+} rg_attn_probs_args;
+int rg_attn_probs(const rg_attn_probs_args* args /* host */, int dtype, void* stream);
+/* rg_attn_cross_probs: the map of the decoder-encoder attention, which sees L copies of one encoder state (quirk Q1) -- a closed
+ * form, the reference's bits: for every head and query row float32(1) / float32(n_b) at the keys with enc_ids[b, key] != pad_value
+ * (n_b their count), 0 at the others; float32(1) / float32(L) everywhere if n_b == 0.  Same probs / b_stride addressing; L <= 32768. */
+int rg_attn_cross_probs(const int64_t* enc_ids, int64_t pad_value, float* probs, long long b_stride, int B, int L, int H, void* stream);
+/* rg_attn_rollout: attention rollout (Abnar & Zuidema 2020) from one query position through a stack's maps [B,N,H,L,L] (contiguous)
+ * to its input positions: r = e_query; for l = N-1 .. 0: r <- alpha r + (1 - alpha) (r . Abar_l), Abar_l = (1/H) sum_h maps[b, l, h];
+ * out [B, L] = r (rows sum to 1 when the maps' rows do).  query [B] int32 on the device, or NULL = position L - 1.  One workgroup per
+ * sequence, heads then queries added in ascending order (fixed bits), rows with r[q] == 0 skipped.  L <= 2048.
+ * RG_ERR_INVALID for a query[b] outside 0 .. L-1: checked on the host before any launch (one copy-back and one wait on the stream,
+ * only when query != NULL). */
+int rg_attn_rollout(const float* maps, const int* query, float alpha, float* out, int B, int N, int H, int L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

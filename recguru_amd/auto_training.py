@@ -120,6 +120,25 @@ def recommend(model, enc_in, dec_in, k, param, exclude_seen=True, sas=False, amo
     return ids, scores
 
 
+def explain(model, enc_in, dec_in, param, alpha=0.5):
+    """training.explain for the single-domain model: the attention maps of get_embedding's path (eval(), no_grad) -- enc_self from
+    the encoder, dec_self / dec_enc from the recommend stack (the shared decoder with dec_rec), each [B, n_layers, H, L, L] f32 --
+    and enc_rollout / dec_rollout [B, L], the rollout of enc_self / dec_self from the last position (hip.attn_rollout).  The model's
+    training flag is left as it was found."""
+    from . import hip
+    m = _unwrap(model)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            _, enc_self = m.AutoEnc.get_seq_embed(enc_in, last_only=True, return_attn=True)
+            _, dec_self, dec_enc = m.get_embedding(enc_in, dec_in, return_attn=True)
+            return {"enc_self": enc_self, "dec_self": dec_self, "dec_enc": dec_enc,
+                    "enc_rollout": hip.attn_rollout(enc_self, alpha=alpha), "dec_rollout": hip.attn_rollout(dec_self, alpha=alpha)}
+    finally:
+        model.train(was_training)
+
+
 def evaluation_full(model_train, data_loader, de, param_config, k_val=None, sas=False, among=None):
     """evaluation() with unsampled metrics: the exact rank of every validation / test target among all catalogue items (the
     full-catalogue kernel); the loader's sampled candidates are ignored.  Returns one result dict in evaluation()'s layout.

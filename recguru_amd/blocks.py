@@ -90,6 +90,14 @@ class PositionalEncodingM(nn.Module):
         return _rate(self.dropout_rate) if self.training else 0.0
 
 
+def check_return_attn(module):
+    """return_attn=True offers the softmax, not a dropped sample of it: a module in training mode with a dropout rate > 0 is
+    refused, before any launch."""
+    if module.training and any(_rate(getattr(m, "dropout_rate", None)) > 0 for m in module.modules()):
+        raise ValueError("return_attn=True needs eval() or a dropout rate of 0: the attention maps are the softmax, and under "
+                         "active dropout the forward uses a dropped sample of it")
+
+
 def check_positions(pos, L):
     """A batch longer than the positional table has no rows to read: refuse it before any launch."""
     rows = pos.table().shape[0]
@@ -179,22 +187,36 @@ class EncoderM(nn.Module):
         self.layers = nn.ModuleList([EncoderLayer(d_model, d_ff, d_k, d_v, n_heads, device, dropout)
                                      for _ in range(n_layers)])
 
-    def forward(self, x, key_ids, pad_value, pad_mask, last_only=False):
+    def forward(self, x, key_ids, pad_value, pad_mask, last_only=False, return_attn=False):
         """last_only=True returns enc_outputs[:, -1, :] ([B, d]) without computing the other rows of
-        the last layer (identical values and gradients)."""
+        the last layer (identical values and gradients).
+        return_attn=True returns (outputs, enc_self_attns [B, n_layers, H, L, L] f32) like the reference (transformer.py:597-599):
+        the hidden states come from the unchanged layer code, the map of layer l is a side computation on its input
+        (ops.attn_map) written in place -- also under last_only, whose last map is still the full [L, L] one.  4 B N H L^2
+        bytes: an inspection call."""
         n = len(self.layers)
+        maps = None
+        if return_attn:
+            check_return_attn(self)
+            maps = torch.empty(x.shape[0], n, self.layers[0].enc_self_attn.n_heads, x.shape[1], x.shape[1], device=x.device,
+                               dtype=torch.float32)
         # Every layer output is multiplied by pad_mask (:594), so from the second layer on the layer input has exactly-zero
         # rows at padded positions (ops.masked_input: the Q / K / V projection may then use the bias row for them).  The
         # FIRST layer's input only when it provably is the embedding stage `(E[ids] + pe) * pad_mask` of this very mask
         # (transformer.py:105; ops.masked_by) -- an arbitrary caller-supplied x is taken as it is, like the reference does.
         masked = ops.masked_by(x, pad_mask)
         for i, layer in enumerate(self.layers):
+            if maps is not None:
+                att = layer.enc_self_attn
+                ops.attn_map(x, key_ids, pad_value, False, att.n_heads, *att.self_params()[:6], out=maps, layer=i)
             with ops.masked_input(masked):
                 if last_only and i == n - 1:
-                    return layer.forward_last(x, key_ids, pad_value, pad_mask)
+                    x = layer.forward_last(x, key_ids, pad_value, pad_mask)
+                    return (x, maps) if return_attn else x
                 x = layer(x, key_ids, pad_value, pad_mask)
             masked = True
-        return x[:, -1, :] if last_only else x
+        x = x[:, -1, :] if last_only else x
+        return (x, maps) if return_attn else x
 
 
 class DecoderM(nn.Module):
@@ -209,12 +231,26 @@ class DecoderM(nn.Module):
         self.layers = nn.ModuleList([DecoderLayer(d_model, d_ff, d_k, d_v, n_heads, device, dropout)
                                      for _ in range(n_layers)])
 
-    def forward(self, x, u, dec_ids, enc_ids, pad_m):
+    def forward(self, x, u, dec_ids, enc_ids, pad_m, return_attn=False):
         """enc_ids: the encoder input ids; their (== 0) positions are the masked keys of the
-        decoder-encoder attention (AutoEnc4Rec_cross.py:134) -- only needed when dropout is active."""
+        decoder-encoder attention (AutoEnc4Rec_cross.py:134) -- only needed when dropout is active or the maps are asked for.
+        return_attn=True returns (outputs, dec_self_attns, dec_enc_attns), each [B, n_layers, H, L, L] f32 (transformer.py:546-549):
+        the self maps as in EncoderM (causal + key-pad(dec_ids == 0)), the decoder-encoder maps in their closed form
+        (hip.attn_cross_probs: uniform over the keys with enc_ids != 0)."""
         masked = ops.masked_by(x, pad_m)     # same contract as EncoderM (layer outputs: transformer.py:539)
-        for layer in self.layers:
+        self_maps = cross_maps = None
+        if return_attn:
+            from . import hip
+            check_return_attn(self)
+            shape = (x.shape[0], len(self.layers), self.layers[0].dec_self_attn.n_heads, x.shape[1], x.shape[1])
+            self_maps = torch.empty(shape, device=x.device, dtype=torch.float32)
+            cross_maps = torch.empty(shape, device=x.device, dtype=torch.float32)
+        for i, layer in enumerate(self.layers):
+            if return_attn:
+                att = layer.dec_self_attn
+                ops.attn_map(x, dec_ids, 0, True, att.n_heads, *att.self_params()[:6], out=self_maps, layer=i)
+                hip.attn_cross_probs(enc_ids.contiguous(), 0, att.n_heads, out=cross_maps, layer=i)
             with ops.masked_input(masked):
                 x = layer(x, u, dec_ids, enc_ids, pad_m)
             masked = True
-        return x
+        return (x, self_maps, cross_maps) if return_attn else x

@@ -112,7 +112,8 @@ SYMBOLS = ["rg_last_error", "rg_version", "rg_gemm_nt", "rg_gemm_tn", "rg_attn_f
            "rg_shared_ce_supported", "rg_shared_ce_bwd_workspace", "rg_shared_ce_fwd", "rg_shared_ce_bwd",
            "rg_topk_workspace", "rg_topk_scores", "rg_topk_list_workspace", "rg_topk_list",
            "rg_grad_sqnorm_multi", "rg_adam_multi_dev2",
-           "rg_pos_grad_workspace", "rg_pos_grad"]
+           "rg_pos_grad_workspace", "rg_pos_grad",
+           "rg_attn_probs", "rg_attn_cross_probs", "rg_attn_rollout"]
 LOSS_SAMPLED_CE, LOSS_BPR, LOSS_BPR_SAS = 0, 1, 2
 c_ll = ctypes.c_longlong
 
@@ -572,6 +573,64 @@ def attn_bwd(qkv, dctx, ctx, lse, key_ids, pad_value, causal, H, drop_p=0.0, see
 
 def _vp(t):
     return ctypes.c_void_p(_p(t))
+
+
+class AttnProbsArgs(ctypes.Structure):
+    _fields_ = [("qkv", c_p), ("key_ids", c_p), ("pad_value", c_l), ("causal", c_i), ("probs", c_p), ("b_stride", ctypes.c_longlong),
+                ("B", c_i), ("L", c_i), ("H", c_i), ("dk", c_i), ("scale", c_f)]
+
+
+def _map_dest(out, layer, B, H, L, dev):
+    """(tensor to return, its first element to write, elements between sequences) of a map launch: a new [B,H,L,L] f32 tensor, a
+    given one, or layer `layer` of a given [B,N,H,L,L] tensor written in place."""
+    if out is None:
+        assert layer is None
+        out = torch.empty(B, H, L, L, device=dev, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous()
+    if layer is None:
+        assert tuple(out.shape) == (B, H, L, L)
+        return out, out.data_ptr(), H * L * L
+    assert out.dim() == 5 and (out.shape[0],) + tuple(out.shape[2:]) == (B, H, L, L) and 0 <= int(layer) < out.shape[1]
+    return out, out.data_ptr() + 4 * int(layer) * H * L * L, out.shape[1] * H * L * L
+
+
+def attn_probs(qkv, key_ids, pad_value, H, causal, out=None, layer=None):
+    """The attention map softmax(mask(Q K^T / sqrt(32))) of qkv [B,L,3*H*32] (token-major q | k | v; v is not read) under attn_fwd's
+    masking contract -> [B,H,L,L] f32 (rg_attn_probs; 1 <= L <= 2048).  out: a [B,H,L,L] f32 tensor to fill, or with layer = l a
+    [B,N,H,L,L] tensor whose layer l is written in place (the others are not touched).  No gradient, no dropout."""
+    B, L, P3 = qkv.shape
+    assert P3 == 3 * H * 32 and qkv.is_contiguous() and key_ids.dtype == torch.int64 and key_ids.is_contiguous() and key_ids.numel() == B * L
+    out, ptr, stride = _map_dest(out, layer, B, H, L, qkv.device)
+    a = AttnProbsArgs(_p(qkv), _p(key_ids), int(pad_value), int(bool(causal)), ptr, stride, B, L, H, 32, 1.0 / (32 ** 0.5))
+    _check(lib().rg_attn_probs(ctypes.byref(a), mt_of(qkv), _stream()), "rg_attn_probs")
+    return out
+
+
+def attn_cross_probs(enc_ids, pad_value, H, out=None, layer=None):
+    """The map of the decoder-encoder attention over L copies of one encoder state (quirk Q1), in closed form: every row uniform
+    over the keys with enc_ids != pad_value (over all L if there is none) -> [B,H,L,L] f32 (rg_attn_cross_probs).  out / layer as
+    in attn_probs."""
+    B, L = enc_ids.shape
+    assert enc_ids.dtype == torch.int64 and enc_ids.is_contiguous()
+    out, ptr, stride = _map_dest(out, layer, B, H, L, enc_ids.device)
+    _check(lib().rg_attn_cross_probs(_vp(enc_ids), c_l(int(pad_value)), c_p(ptr), c_ll(stride), B, L, H, _stream()), "rg_attn_cross_probs")
+    return out
+
+
+def attn_rollout(maps, query=None, alpha=0.5, out=None):
+    """Attention rollout of a stack's maps [B,N,H,L,L] f32 from position query[b] (int tensor [B]; None: the last position) to the
+    input positions -> [B,L] f32 (rg_attn_rollout): r = e_query, then for l = N-1 .. 0: r <- alpha r + (1 - alpha) r . mean_h(maps[:, l]).
+    A query outside 0 .. L-1 is refused before any launch (with a query the call waits for the stream once)."""
+    assert maps.dim() == 5 and maps.dtype == torch.float32 and maps.is_contiguous() and maps.shape[3] == maps.shape[4]
+    B, N, H, L, _ = maps.shape
+    if query is not None:
+        assert query.numel() == B and not query.dtype.is_floating_point
+        query = query.to(device=maps.device, dtype=torch.int32).contiguous()
+    if out is None:
+        out = torch.empty(B, L, device=maps.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, L)
+    _check(lib().rg_attn_rollout(_vp(maps), _vp(query), c_f(float(alpha)), _vp(out), B, N, H, L, _stream()), "rg_attn_rollout")
+    return out
 
 
 def embed_pe_fwd(table, pe, ids, mask, L, drop_p=0.0, seed=0, mirror=False):
@@ -1884,7 +1943,8 @@ _WORK = {"full_ce_fwd": _work_full_ce_fwd, "full_ce_dw": _work_full_ce_dw, "shar
          "embed_pe_fwd": _work_embed_fwd, "item_loss_fwd": _work_item_loss, "item_loss_bwd": _work_item_loss}
 _PLAIN = ["dropout_", "cross_rows", "adam_multi", "adam_multi_dev", "adam_multi_dev2", "grad_sqnorm_multi", "disc_rows", "item_loss_bwd_binned", "embed_scatter_bwd", "bcast_add_ln", "seq_sum", "colsum", "outer_posmask", "interpolate",
           "gp_penalty", "sum_into", "adam", "cast", "attn_lastq_fwd", "attn_lastq_bwd", "cross_drop_scale", "seq_wsum",
-          "embed_scatter_bwd_binned", "scale_dev", "dropout_gelu", "add_drop_ln", "mse", "cross_add_ln"]
+          "embed_scatter_bwd_binned", "scale_dev", "dropout_gelu", "add_drop_ln", "mse", "cross_add_ln",
+          "attn_probs", "attn_cross_probs", "attn_rollout"]
 
 
 def start_profile():

@@ -6,8 +6,8 @@ Same class names, constructor signatures, method names and state_dict keys as th
   MyRec          GURU/AutoEnc4Rec.py:20-133         (wrapper: recon + recommender decoder)
   Discriminator  GURU/tools/utils.py:30-57
 so reference checkpoints load with load_state_dict and the reference's drivers can call them.
-Differences a caller can observe: attention maps are not returned (every hot-path
-caller discards them); forward() returns a SampledLogits handle instead of a dense [B,L,k+1]
+Differences a caller can observe: attention maps are returned only on request
+(return_attn=True; every hot-path caller discards them); forward() returns a SampledLogits handle instead of a dense [B,L,k+1]
 tensor so that loss_ae can run the fused gather-dot-loss kernel -- call .dense() for the tensor.
 """
 import numpy as np
@@ -205,40 +205,53 @@ class MyAuto4Rec_c(nn.Module):
         return self.encoder_a if domain == "a" else self.encoder_b
 
     # ---- reference surface --------------------------------------------------------------------
-    def get_seq_embed(self, enc_inputs, domain="a", mask=None, last_only=False):
+    def get_seq_embed(self, enc_inputs, domain="a", mask=None, last_only=False, return_attn=False):
         """AutoEnc4Rec_cross.py:93-115.  The key-pad value is the EOS id vocab_size_{a|b} (quirk Q2).
-        last_only=True returns just [:, -1, :] (what every hot-path caller slices out)."""
+        last_only=True returns just [:, -1, :] (what every hot-path caller slices out).
+        return_attn=True returns (enc_outputs, enc_self_attns [B, n_layers, H, L, L] f32), the reference's tuple (:115)."""
+        if return_attn:
+            blocks.check_return_attn(self)
         L = enc_inputs.shape[1]
         mask = mask.reshape(-1, L)
         x = self._embed(enc_inputs, domain, mask)
         pad_value = self.param.vocab_size_a if domain == "a" else self.param.vocab_size_b
-        return self._encoder(domain)(x, enc_inputs, pad_value, mask, last_only=last_only)
+        return self._encoder(domain)(x, enc_inputs, pad_value, mask, last_only=last_only, return_attn=return_attn)
 
-    def _decode(self, stack, enc_inputs, dec_inputs, domain, mask, d_mask, detach_enc=False):
+    def _decode(self, stack, enc_inputs, dec_inputs, domain, mask, d_mask, detach_enc=False, return_attn=False):
+        if return_attn:
+            blocks.check_return_attn(self)
         L = self.param.enc_maxlen
         u = self.get_seq_embed(enc_inputs, domain, mask.reshape(-1, L), last_only=True)
         if detach_enc:
             u = u.detach()
         x = self._embed(dec_inputs, domain, d_mask)
-        return stack(x, u.contiguous(), dec_inputs, enc_inputs, d_mask)
+        return stack(x, u.contiguous(), dec_inputs, enc_inputs, d_mask, return_attn=return_attn)
 
-    def get_dec_out(self, enc_inputs, dec_inputs, domain="a", mask=None):
-        """AutoEnc4Rec_cross.py:117-147: decoder pad mask comes from enc_inputs (quirk Q5)."""
+    def get_dec_out(self, enc_inputs, dec_inputs, domain="a", mask=None, return_attn=False):
+        """AutoEnc4Rec_cross.py:117-147: decoder pad mask comes from enc_inputs (quirk Q5).
+        return_attn=True fills the two map slots: (dec_outputs, dec_self_attns, dec_enc_attns), each map [B, n_layers, H, L, L] f32."""
+        if return_attn:
+            blocks.check_return_attn(self)
         d_mask = _f32_mask(enc_inputs, self.param.pad_index)
         if self.dec_share:
             stack = self.decoder
         else:
             stack = self.decoder_a if domain == "a" else self.decoder_b
+        if return_attn:
+            return self._decode(stack, enc_inputs, dec_inputs, domain, mask, d_mask, return_attn=True)
         return self._decode(stack, enc_inputs, dec_inputs, domain, mask, d_mask), None, None
 
-    def recommend_forward(self, enc_in, dec_in, domain, mask):
-        """AutoEnc4Rec_cross.py:149-183: pad mask from dec_in; encoder state detached if fixed_enc."""
+    def recommend_forward(self, enc_in, dec_in, domain, mask, return_attn=False):
+        """AutoEnc4Rec_cross.py:149-183: pad mask from dec_in; encoder state detached if fixed_enc.
+        return_attn=True returns (h, dec_self_attns, dec_enc_attns) of the recommender stack."""
+        if return_attn:
+            blocks.check_return_attn(self)
         d_mask = _f32_mask(dec_in, self.param.pad_index)
         if self.dec_rec:
             stack = self.decoder_a if domain == "a" else self.decoder_b
         else:
             stack = self.recommend_a if domain == "a" else self.recommend_b
-        return self._decode(stack, enc_in, dec_in, domain, mask, d_mask, detach_enc=bool(self.param.fixed_enc))
+        return self._decode(stack, enc_in, dec_in, domain, mask, d_mask, detach_enc=bool(self.param.fixed_enc), return_attn=return_attn)
 
     def item_table(self, domain):
         return self.src_emb_a.weight if domain == "a" else self.src_emb_b.weight
@@ -289,22 +302,34 @@ class MyAuto4Rec(nn.Module):
         return ops.embed_pe(self.src_emb.weight, self.pos_emb.table(), ids, mask, skip_row=self.pad_index,
                             drop_p=self.pos_emb.drop_p())
 
-    def get_seq_embed(self, enc_inputs, last_only=False):
-        """AutoEnc4Rec.py:175-184: real pad id for both the row mask and the key mask."""
+    def get_seq_embed(self, enc_inputs, last_only=False, return_attn=False):
+        """AutoEnc4Rec.py:175-184: real pad id for both the row mask and the key mask.
+        return_attn=True fills the map slot: (enc_outputs, enc_self_attns [B, n_layers, H, L, L] f32), the reference's tuple (:184)."""
+        if return_attn:
+            blocks.check_return_attn(self)
         mask = _f32_mask(enc_inputs, self.pad_index)
         x = self._embed(enc_inputs, mask)
+        if return_attn:
+            return self.encoder(x, enc_inputs, self.pad_index, mask, last_only=last_only, return_attn=True)
         return self.encoder(x, enc_inputs, self.pad_index, mask, last_only=last_only), None
 
-    def decode_with(self, stack, enc_inputs, dec_inputs, detach_enc=False):
+    def decode_with(self, stack, enc_inputs, dec_inputs, detach_enc=False, return_attn=False):
+        """The decoder `stack` over the encoder's last state; return_attn=True returns (h, dec_self_attns, dec_enc_attns)."""
+        if return_attn:
+            blocks.check_return_attn(self)
+            blocks.check_return_attn(stack)          # (MyRec's recommender stack is no child of this module)
         u, _ = self.get_seq_embed(enc_inputs, last_only=True)
         if detach_enc:
             u = u.detach()
         mask = _f32_mask(dec_inputs, self.pad_index)
         x = self._embed(dec_inputs, mask)
-        return stack(x, u.contiguous(), dec_inputs, enc_inputs, mask)
+        return stack(x, u.contiguous(), dec_inputs, enc_inputs, mask, return_attn=return_attn)
 
-    def get_dec_out(self, enc_inputs, dec_inputs):
-        """AutoEnc4Rec.py:186-204: decoder pad mask from dec_inputs."""
+    def get_dec_out(self, enc_inputs, dec_inputs, return_attn=False):
+        """AutoEnc4Rec.py:186-204: decoder pad mask from dec_inputs.
+        return_attn=True fills the two map slots: (dec_outputs, dec_self_attns, dec_enc_attns)."""
+        if return_attn:
+            return self.decode_with(self.decoder, enc_inputs, dec_inputs, return_attn=True)
         return self.decode_with(self.decoder, enc_inputs, dec_inputs), None, None
 
     def forward(self, enc_inputs, dec_inputs, dec_outputs, n_items):
@@ -336,11 +361,15 @@ class MyRec(nn.Module):
         self.dec_rec = dec_rec
         self.param = param
 
-    def get_embedding(self, enc_in, dec_in):
-        """AutoEnc4Rec.py:55-85."""
+    def get_embedding(self, enc_in, dec_in, return_attn=False):
+        """AutoEnc4Rec.py:55-85.  return_attn=True returns (h, dec_self_attns, dec_enc_attns) of the recommender stack (the shared
+        decoder with dec_rec), each map [B, n_layers, H, L, L] f32."""
+        if return_attn:
+            blocks.check_return_attn(self)
         if self.dec_rec:
-            return self.AutoEnc.get_dec_out(enc_in, dec_in)[0]
-        return self.AutoEnc.decode_with(self.recommend, enc_in, dec_in, detach_enc=bool(self.fix_enc))
+            out = self.AutoEnc.get_dec_out(enc_in, dec_in, return_attn=return_attn)
+            return out if return_attn else out[0]
+        return self.AutoEnc.decode_with(self.recommend, enc_in, dec_in, detach_enc=bool(self.fix_enc), return_attn=return_attn)
 
     def forward(self, enc_in, dec_in, dec_out, n_items, recon=False):
         """AutoEnc4Rec.py:98-133.  recon=True: reconstruction logits handle; else the (p, n) logits of

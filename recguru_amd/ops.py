@@ -713,6 +713,19 @@ def _qkv_attn_fwd(x2, B, L, key_ids, pad_value, causal, H, Wq, bq, Wk, bk, Wv, b
     return qkv, ctx_, lse
 
 
+def attn_map(x, key_ids, pad_value, causal, H, Wq, bq, Wk, bk, Wv, bv, out=None, layer=None):
+    """The self-attention map [B, H, L, L] f32 of one layer from the LAYER INPUT x [B, L, d] and the layer's WQ / WK / WV
+    (return_attn=True of the stacks, blocks.py): the tier's plain projection -- token-major, every row, nothing skipped -- then
+    hip.attn_probs.  A side computation under no_grad: it takes no part in autograd and reads nothing the layer's forward wrote.
+    out / layer: write layer `layer` of a [B, N, H, L, L] tensor in place.  The forward's fused x-input forms project inside the
+    attention kernel, so this map agrees with the probabilities the forward used to operand rounding, not to the bit."""
+    with torch.no_grad():
+        B, L, d = x.shape
+        x2 = x.detach().contiguous().view(B * L, d)
+        qkv = hip.gemm_nt(x2, shadow_cat((Wq, Wk, Wv)), bias_cat((bq, bk, bv)))
+        return hip.attn_probs(qkv.view(B, L, -1), key_ids.contiguous(), int(pad_value), H, bool(causal), out=out, layer=layer)
+
+
 def _attn_block_fwd(x2, B, L, key_ids, pad_value, causal, H, Wq, bq, Wk, bk, Wv, bv, Wo, bo, g, be, need_grad,
                     drop_p=0.0, seed=0, rowmask=None, x_masked=False):
     """MultiHeadAttention.forward (transformer.py:151-161), unfused (any width): returns y and what backward needs."""

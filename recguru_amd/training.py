@@ -249,6 +249,27 @@ def _last_rec_state(model, enc_in, dec_in, domain, param, device):
     return h[:, -1, :].contiguous()
 
 
+def explain(model, enc_in, dec_in, param, domain="a", device=None, alpha=0.5):
+    """Why was this recommended: the attention maps of the recommender path (the encoder pass and the decoder stack of
+    recommend_forward, run in eval() under no_grad) and their rollout from the last position to the history items.  Returns a dict:
+    enc_self / dec_self / dec_enc [B, n_layers, H, L, L] f32 (the decoder is the recommend stack, or the domain's decoder with dec_rec),
+    enc_rollout / dec_rollout [B, L] f32 (hip.attn_rollout of enc_self / dec_self, rows sum to 1).  Each map tensor takes
+    4 B n_layers H L^2 bytes: a call for tens to hundreds of users.  The model's training flag is left as it was found."""
+    from . import hip
+    m = _unwrap(model)
+    was_training = model.training
+    model.eval()
+    try:
+        enc_mask = get_pad_mask(dec_in, param.pad_index, device if device is not None else dec_in.device)
+        with torch.no_grad():
+            _, enc_self = m.get_seq_embed(enc_in, domain, enc_mask, last_only=True, return_attn=True)
+            _, dec_self, dec_enc = m.recommend_forward(enc_in, dec_in, domain, enc_mask, return_attn=True)
+            return {"enc_self": enc_self, "dec_self": dec_self, "dec_enc": dec_enc,
+                    "enc_rollout": hip.attn_rollout(enc_self, alpha=alpha), "dec_rollout": hip.attn_rollout(dec_self, alpha=alpha)}
+    finally:
+        model.train(was_training)
+
+
 def get_scores(model, enc_in, dec_in, target, n_items, param, sas=False, domain="a", device=None):
     """gan_training.py:58-87: [B, 1 + candidate_size] scores, column 0 = the held-out target (torch.squeeze'd like
     the reference).  The candidate gather, concatenation and batched matmul are one HIP kernel."""
