@@ -124,6 +124,13 @@ def _ver(p):
     return (p.data_ptr(), p._version, getattr(p, "_rg_gen", 0))
 
 
+def _src(ps):
+    """Last member of a cache entry: tensors on the storages the copy was made from.  While the entry lives those storages do, so
+    a matching address IS that storage: p.data replaced twice between two calls would otherwise get the freed block back, with
+    the _version and bump count the entry recorded, and the old weights would be served (hip._LIVE keeps its masks the same way)."""
+    return tuple(p.detach() for p in ps)
+
+
 def shadow(p, transpose=False, pack=False, split=False):
     """Operand-tier copy of a 2-D f32 parameter: [out,in] or, transposed, [in,out]; pack=True: in the MFMA-fragment-packed
     layout (hip.CAST_PACK) the fused kernels read; split=True (honoured in the bf16x3 tier only, with pack): the presplit form
@@ -131,7 +138,11 @@ def shadow(p, transpose=False, pack=False, split=False):
     LIFETIME: the returned tensor is valid until the SECOND optimizer step after it was handed out -- refresh_shadows()
     rewrites two alternating destination buffers in place, so a holder that keeps a shadow across two steps (an autograd graph
     retained over steps, a table captured once before a training loop) would read newer weights.  Every use in this package
-    takes the shadow at launch time; callers that need a stable copy must clone it."""
+    takes the shadow at launch time; callers that need a stable copy must clone it.
+    CURRENCY: a copy is current when (data_ptr, _version, bump count) of the parameter match -- in-place torch ops under no_grad,
+    load_state_dict and a replaced p.data all move one of them.  A write through p.data (p.data.copy_()) or through a raw pointer
+    (the optimizer's kernels) moves NONE: it must be followed by bump(p), and that is sufficient -- the next call returns the new
+    weights' bits (tests/test_shadow_coherence_gpu.py holds every hand-out to a plain-torch restatement, bit for bit)."""
     transpose = int(bool(transpose)) | (hip.CAST_PACK if pack else 0)       # cast mode; rides in the key's transpose slot
     if split and pack and hip.SPLIT_OPERANDS:
         transpose |= hip.CAST_SPLIT
@@ -143,7 +154,8 @@ def shadow(p, transpose=False, pack=False, split=False):
     # the entry must belong to THIS parameter object: id() and even the data pointer of a collected parameter are
     # reused by later ones (a stale copy of another model's weight surfaced once in ~25 runs of the test suite)
     if ent is None or ent[0] != ver or ent[2][0]() is not p:
-        ent = (ver, hip.cast(p.detach(), _COMPUTE, transpose=transpose), (weakref.ref(p),))
+        src = p.detach()
+        ent = (ver, hip.cast(src, _COMPUTE, transpose=transpose), (weakref.ref(p),), (src,))      # (src: see _src)
         _SHADOWS[key] = ent
     return ent[1]
 
@@ -154,9 +166,10 @@ def shadow_cat(ps, transpose=False):
     ver = tuple(_ver(p) for p in ps)
     ent = _SHADOWS.get(key)
     if ent is None or ent[0] != ver or any(r() is not p for r, p in zip(ent[2], ps)):
-        w = torch.cat([p.detach() for p in ps], 0).contiguous()
+        src = _src(ps)
+        w = torch.cat(src, 0).contiguous()
         ent = (ver, hip.cast(w, _COMPUTE, transpose=transpose) if (transpose or _COMPUTE != torch.float32) else w,
-               tuple(weakref.ref(p) for p in ps))
+               tuple(weakref.ref(p) for p in ps), src)
         _SHADOWS[key] = ent
     return ent[1]
 
@@ -168,7 +181,8 @@ def bias_cat(ps):
     ver = tuple(_ver(p) for p in ps)
     ent = _SHADOWS.get(key)
     if ent is None or ent[0] != ver or any(r() is not p for r, p in zip(ent[2], ps)):
-        ent = (ver, torch.cat([p.detach() for p in ps]), tuple(weakref.ref(p) for p in ps))
+        src = _src(ps)
+        ent = (ver, torch.cat(src), tuple(weakref.ref(p) for p in ps), src)
         _SHADOWS[key] = ent
     return ent[1]
 
@@ -180,8 +194,9 @@ def pad_rows_cat(ps, H):
     ver = tuple(_ver(p) for p in ps)
     ent = _SHADOWS.get(key)
     if ent is None or ent[0] != ver or any(r() is not p for r, p in zip(ent[2], ps)):
-        b = torch.cat([p.detach().reshape(H, 32) for p in ps] + [torch.zeros(1, 32, device=ps[0].device)], 0)
-        ent = (ver, b.to(_COMPUTE).contiguous(), tuple(weakref.ref(p) for p in ps))
+        src = _src(ps)
+        b = torch.cat([s.reshape(H, 32) for s in src] + [torch.zeros(1, 32, device=ps[0].device)], 0)
+        ent = (ver, b.to(_COMPUTE).contiguous(), tuple(weakref.ref(p) for p in ps), src)
         _SHADOWS[key] = ent
     return ent[1]
 
@@ -249,13 +264,15 @@ def refresh_shadows(params):
             n = ((r + 31) // 32) * ((c + 31) // 32)
             rows.append(np.stack([np.full(n, i, dtype=np.int32), np.arange(n, dtype=np.int32)], 1))
         tiles = torch.from_numpy(np.concatenate(rows, 0)).to(dev)
-        ent = _REFRESH_CACHE[sig] = {"gens": gens, "tiles": tiles, "turn": 0, "dtype": _COMPUTE}
+        # (srcs: the cached entry keeps the source storages alive, so its signature's addresses stay theirs -- _src -- and a
+        # steady-state refresh builds nothing per entry)
+        ent = _REFRESH_CACHE[sig] = {"gens": gens, "tiles": tiles, "turn": 0, "dtype": _COMPUTE, "srcs": [_src(ps) for _, ps in todo]}
     outs, tbl, _ = ent["gens"][ent["turn"]]
     ent["turn"] ^= 1
     hip.cast_multi(tbl, ent["tiles"], ent["tiles"].shape[0], _COMPUTE)
-    for (key, ps), dst in zip(todo, outs):
+    for (key, ps), dst, src in zip(todo, outs, ent["srcs"]):
         ver = _ver(ps[0]) if len(key) == 3 else tuple(_ver(p) for p in ps)
-        _SHADOWS[key] = (ver, dst, tuple(weakref.ref(p) for p in ps))
+        _SHADOWS[key] = (ver, dst, tuple(weakref.ref(p) for p in ps), src)
 
 
 _REFRESH_CACHE = {}
