@@ -690,6 +690,42 @@ typedef struct {
 size_t rg_topk_list_workspace(int B, int d, long long n_list, int K);   /* 0 = unsupported shape */
 int rg_topk_list(const rg_topk_list_args* args /* host */, int dtype, void* stream);
 
+/* ---- wide top-K, 1 <= K <= 1024 (csrc/topk_wide.hip) -----------------------------------------------------
+ * rg_topk_scores / rg_topk_list without the rank, for the K a second-stage ranker asks for: per user the K eligible ids with the
+ * highest scores, score descending, ties by ascending id, table rows in both forms; fewer than K eligible: trailing slots hold
+ * id -1 and score -inf.  One args struct serves both catalogue forms: rows == NULL is the range form (first_row, n_rows; n_list and
+ * table_rows are not read), otherwise rows [n_list] is a strictly ascending list of table rows shared by the batch (first_row and
+ * n_rows are not read).  Exclusion ids outside the catalogue or the list count for nothing.  topk_ids or topk_scores may be NULL, not
+ * both.  d in {64, 128, 256}, dtype RG_BF16 / RG_X3, n_rows, n_list, table_rows < 2^31; anything else is RG_ERR_UNSUPPORTED.
+ * Same score function and the same 64-bit key (score image, then 0xFFFFFFFF - row or list position) as the calls above: for
+ * K <= 128 the result equals theirs bit for bit, for any K it is the K largest keys of the eligible set.  The K-th key is found
+ * by a radix select on the key, 8 bits per pass over the catalogue (at most 7 passes, the number decided on the device; the
+ * scores are recomputed in every pass, [B, n_rows] is never formed), the keys at or above it are collected and sorted per user.
+ * Integer atomics only: bit-identical across repeats, batch splits and both libraries.
+ * The range form enqueues and returns; the list form copies one word back and waits for the stream once (the device-side check
+ * of rows: RG_ERR_INVALID names the first offending position and its value).  A refused call launches no scoring kernel and
+ * writes no output.
+ * Workspace: 256 + align256(32 B) + B (1024 + 16384) bytes -- a head, 32 bytes of state, 256 bins and a buffer of 2048 keys per
+ * user; a function of B alone among the supported shapes.  The workspace query returns 0 for an unsupported shape.  The first
+ * 32-bit word of the workspace is a fault word, 0 after every call that worked as designed (bit 0: a key did not fit a user's
+ * buffer and was dropped -- nothing is ever stored past a buffer; bit 1: a pass counted fewer keys in a bucket than the pass
+ * before; bit 2: a user's selection had not ended after the last pass and nothing was collected for it). */
+typedef struct {
+  const void* h;                 /* [B, d]   operand dtype */
+  const void* table;             /* [rows, d] operand dtype */
+  long long first_row, n_rows;   /* range form: the catalogue is rows first_row .. first_row + n_rows - 1 of table */
+  const int64_t* rows;           /* list form: [n_list] strictly ascending table rows; NULL = range form */
+  long long n_list, table_rows;  /* list form */
+  const int64_t* excl;           /* CSR as in rg_topk_args, or both NULL */
+  const int64_t* excl_off;
+  int64_t* topk_ids;             /* [B, K] out, or NULL */
+  float* topk_scores;            /* [B, K] out, or NULL */
+  void* workspace; size_t workspace_bytes;
+  int B, d, K;
+} rg_topk_wide_args;
+size_t rg_topk_wide_workspace(int B, int d, long long n_rows, int K);   /* n_rows: or n_list; 0 = unsupported shape */
+int rg_topk_wide(const rg_topk_wide_args* args /* host */, int dtype, void* stream);
+
 /* ---- fused post-attention block, forward -------------------------------------------------------------
  * y = LN(ctx.Wo^T + bo + x) [; y = LN(y + o_bcast[b])] ; out = LN(gelu(y.W1^T + b1).W2^T + b2 + y) * rowmask
  * = MultiHeadAttention tail (Transformer/transformer.py:160-161) [+ collapsed dec_enc_attn, :259, Q1]

@@ -17,7 +17,7 @@ import torch
 from . import ops, profiling
 from .models import check_recon_handle
 from .optim import Adam, norm_of, options as adam_options
-from .training import _extend_result, _item_list, _new_result, plot, seen_rows
+from .training import TOPK_NARROW_MAX_K, _extend_result, _item_list, _new_result, plot, seen_rows
 
 
 def _unwrap(model):
@@ -104,15 +104,21 @@ def item_list(among, param, device=None):
 def recommend(model, enc_in, dec_in, k, param, exclude_seen=True, sas=False, among=None):
     """training.recommend for the single-domain model: the k catalogue items (ids 1 .. vocab_size - 1) that score highest against
     the last recommender-decoder state, (ids [B, k] int64, scores [B, k] f32); with exclude_seen none of the user's own items.
-    among (item ids): the k best of those ids only (hip.topk_list)."""
+    among (item ids): the k best of those ids only (hip.topk_list).  129 <= k <= 1024: hip.topk_wide; k > 1024: ValueError."""
     if sas:
         raise NotImplementedError("SASRec scoring is outside the hot path")
     from . import hip
+    if int(k) > hip.TOPK_WIDE_MAX_K:
+        raise ValueError("recommend: k = %d is above the limit of %d items per user" % (int(k), hip.TOPK_WIDE_MAX_K))
     m = _unwrap(model)
     rows = None if among is None else item_list(among, param, enc_in.device)
     with torch.no_grad():
         h = m.get_embedding(enc_in, dec_in)[:, -1, :].contiguous()
     excl, off = seen_rows(enc_in, 0, param.vocab_size) if exclude_seen else (None, None)
+    if int(k) > TOPK_NARROW_MAX_K:                                # 129 .. 1024: hip.topk_wide, either form
+        if rows is not None:
+            return hip.topk_wide(h, ops.shadow(m.AutoEnc.src_emb.weight), k, rows=rows, excl=excl, excl_off=off)
+        return hip.topk_wide(h, ops.shadow(m.AutoEnc.src_emb.weight), k, 1, param.vocab_size - 1, excl=excl, excl_off=off)
     if rows is not None:
         ids, scores, _ = hip.topk_list(h, ops.shadow(m.AutoEnc.src_emb.weight), k, rows, excl=excl, excl_off=off)
         return ids, scores

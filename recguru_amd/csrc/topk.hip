@@ -34,86 +34,10 @@
 #include <vector>
 
 #include "rg_common.hip.h"
+#include "topk_common.hip.h"          // tk_scores(), the key, the row / user loads, tk_excluded, the list helpers, tk_slices: shared with topk_wide.hip
 #include "../../include/recguru_hip.h"
 
 namespace {
-
-constexpr int TK_WAVES = 4;
-constexpr int TK_THREADS = TK_WAVES * RG_WAVE;
-constexpr int TK_UB = TK_WAVES * 16;        // users per workgroup
-constexpr int TK_MAX_SLICES = 64;
-constexpr int TK_TARGET_WGS = 1024;
-constexpr int TK_MAX_K = 128;
-constexpr int TK_MERGE_THREADS = 256;
-
-typedef unsigned long long tk_key;          // (order-preserving image of the score) << 32 | (0xFFFFFFFF - row in the catalogue); 0 = empty
-
-__device__ __forceinline__ tk_key tk_make_key(float s, unsigned int row) {
-  const unsigned int u = __float_as_uint(s + 0.f);          // -0 -> +0: equal scores, equal images
-  const unsigned int o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((tk_key)o << 32) | (tk_key)(0xFFFFFFFFu - row);
-}
-__device__ __forceinline__ float tk_key_score(tk_key k) {
-  const unsigned int o = (unsigned int)(k >> 32);
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
-__device__ __forceinline__ unsigned int tk_key_row(tk_key k) { return 0xFFFFFFFFu - (unsigned int)k; }
-
-__device__ __forceinline__ tk_key tk_readlane(tk_key v, int l) {
-  const unsigned int lo = __builtin_amdgcn_readlane((int)(unsigned int)v, l), hi = __builtin_amdgcn_readlane((int)(unsigned int)(v >> 32), l);
-  return ((tk_key)hi << 32) | lo;
-}
-__device__ __forceinline__ tk_key tk_shfl_xor(tk_key v, int o) {
-  const unsigned int lo = __shfl_xor((int)(unsigned int)v, o), hi = __shfl_xor((int)(unsigned int)(v >> 32), o);
-  return ((tk_key)hi << 32) | lo;
-}
-
-// raw fragment (as loaded) -> MFMA operand: the bf16 tier's is the fragment, the x3 tier's the split pair
-__device__ __forceinline__ void tk_to_op(Frag<__bf16>& o, const Frag<__bf16>& r) { o = r; }
-__device__ __forceinline__ void tk_to_op(FragX3& o, const Frag<x3>& r) { split_x3(r.v, o.hi, o.lo); }
-
-// the score tile: acc reg r of lane (g, i) = A row 4 g + r (a user) . B column i (a catalogue row)
-template <typename T, int KS>
-__device__ __forceinline__ f32x4 tk_scores(const typename OpT<T>::type (&a)[KS], const Frag<T> (&braw)[KS]) {
-  f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    typename OpT<T>::type b;
-    tk_to_op(b, braw[ks]);
-    mma(a[ks], b, acc);
-  }
-  return acc;
-}
-
-// row `row` of src (row < 0: zeros) as the lane's share of KS k-steps
-template <typename T, int D>
-__device__ __forceinline__ void tk_load_row(Frag<T> (&f)[D / 32], const T* __restrict__ src, long long row, int g) {
-#pragma unroll
-  for (int ks = 0; ks < D / 32; ++ks) {
-    if (row >= 0) load_frag(f[ks], src + row * D + ks * 32 + 8 * g);
-    else frag_zero(f[ks]);
-  }
-}
-
-// the wave's 16 users as A operands
-template <typename T, int D>
-__device__ __forceinline__ void tk_load_users(typename OpT<T>::type (&ha)[D / 32], const T* __restrict__ H, long long b, int B, int g) {
-  Frag<T> raw[D / 32];
-  tk_load_row<T, D>(raw, H, b < B ? b : -1, g);
-#pragma unroll
-  for (int ks = 0; ks < D / 32; ++ks) tk_to_op(ha[ks], raw[ks]);
-}
-
-// id in the sorted run ex[lo, hi)?
-__device__ __forceinline__ bool tk_excluded(const int64_t* __restrict__ ex, long long lo, long long hi, long long id) {
-  const long long end = hi;
-  while (lo < hi) {
-    const long long mid = (lo + hi) >> 1;
-    if (ex[mid] < id) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < end && ex[lo] == id;
-}
 
 // ------------------------------------------------------------------------------------------------
 // target scores and the exclusion rows' share of the rank
@@ -200,11 +124,6 @@ __device__ __forceinline__ void tk_insert(volatile tk_key* lst, int K, volatile 
   }
   if (lane == 0) { *thr = w; *wpos = wp; }
   __builtin_amdgcn_wave_barrier();
-}
-
-// table row at position pos of the list (-1 past its end)
-__device__ __forceinline__ int tk_list_id(const int64_t* __restrict__ rows, unsigned int pos, unsigned int n) {
-  return pos < n ? (int)rows[pos] : -1;                         // (table_rows < 2^31: one register)
 }
 
 template <typename T, int D, bool LIST>
@@ -350,11 +269,6 @@ __global__ __launch_bounds__(TK_MERGE_THREADS) void tk_merge_kernel(const tk_key
   }
 }
 
-int tk_slices(int B) {
-  const int nub = (B + TK_UB - 1) / TK_UB;
-  const int s = (TK_TARGET_WGS + nub - 1) / nub;
-  return s < 1 ? 1 : (s > TK_MAX_SLICES ? TK_MAX_SLICES : s);
-}
 size_t tk_tscore_bytes(int B) { return ((size_t)B * sizeof(float) + 255) & ~(size_t)255; }
 bool tk_shape_ok(int B, int d, long long n_rows, int K) {
   return B >= 1 && (d == 64 || d == 128 || d == 256) && K >= 0 && K <= TK_MAX_K && n_rows >= 1 && n_rows < (1LL << 31);
@@ -364,10 +278,7 @@ bool tk_shape_ok(int B, int d, long long n_rows, int K) {
 __global__ __launch_bounds__(256) void tk_list_check_kernel(const int64_t* __restrict__ rows, long long n, long long table_rows,
                                                             unsigned long long* __restrict__ bad) {
   const long long step = (long long)gridDim.x * blockDim.x;
-  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += step) {
-    const long long v = rows[p];
-    if (v < 0 || v >= table_rows || (p > 0 && v <= (long long)rows[p - 1])) atomicMin(bad, (unsigned long long)p);
-  }
+  tk_list_check(rows, n, table_rows, bad, (long long)blockIdx.x * blockDim.x + threadIdx.x, step);
 }
 
 constexpr size_t TK_LIST_WORD_BYTES = 256;          // the check kernel's word, between tscore and the slices' keys

@@ -111,6 +111,7 @@ SYMBOLS = ["rg_last_error", "rg_version", "rg_gemm_nt", "rg_gemm_tn", "rg_attn_f
            "rg_full_ce_supported", "rg_full_ce_fwd", "rg_full_ce_dw",
            "rg_shared_ce_supported", "rg_shared_ce_bwd_workspace", "rg_shared_ce_fwd", "rg_shared_ce_bwd",
            "rg_topk_workspace", "rg_topk_scores", "rg_topk_list_workspace", "rg_topk_list",
+           "rg_topk_wide_workspace", "rg_topk_wide",
            "rg_grad_sqnorm_multi", "rg_adam_multi_dev2",
            "rg_pos_grad_workspace", "rg_pos_grad",
            "rg_attn_probs", "rg_attn_cross_probs", "rg_attn_rollout"]
@@ -1092,6 +1093,65 @@ def topk_list(h, table, k, rows, target=None, excl=None, excl_off=None, want_ran
                      _p(ids), _p(scores), _p(rank), _p(ws), need, B, d, k)
     _check(lib().rg_topk_list(ctypes.byref(a), _full_ce_code(h), _stream()), "rg_topk_list")
     return ids, scores, rank
+
+
+class TopkWideArgs(ctypes.Structure):
+    _fields_ = [("h", c_p), ("table", c_p), ("first_row", c_ll), ("n_rows", c_ll), ("rows", c_p), ("n_list", c_ll), ("table_rows", c_ll),
+                ("excl", c_p), ("excl_off", c_p), ("topk_ids", c_p), ("topk_scores", c_p), ("workspace", c_p),
+                ("workspace_bytes", ctypes.c_size_t), ("B", c_i), ("d", c_i), ("K", c_i)]
+
+
+TOPK_WIDE_MAX_K = 1024
+
+
+def topk_wide(h, table, k, first_row=None, n_rows=None, rows=None, excl=None, excl_off=None):
+    """topk_scores / topk_list without the rank for 1 <= k <= 1024 (rg_topk_wide: a radix select on the kernels' 64-bit key, a few
+    passes over the catalogue, the scores recomputed in each; [B, n_rows] is never stored): (ids [B,k] int64, scores [B,k] f32), score
+    descending, ties by ascending id, -1 / -inf past the eligible ones.  Either first_row and n_rows (the range form, enqueued without
+    a wait) or rows [n_list] int64, strictly ascending table rows (the list form: checked on the device, one wait).  For k <= 128 the
+    result equals topk_scores' / topk_list's bit for bit."""
+    B, d = h.shape
+    k = int(k)
+    assert h.is_contiguous() and table.is_contiguous() and table.dtype == h.dtype and table.shape[1] == d
+    assert (rows is None) != (first_row is None and n_rows is None), "either first_row and n_rows, or rows"
+    assert (excl is None) == (excl_off is None)
+    if rows is None:
+        first_row, n_rows, n_list = int(first_row), int(n_rows), 0
+        assert 0 <= first_row and first_row + n_rows <= table.shape[0], "the catalogue rows must lie inside the table"
+        n = n_rows
+    else:
+        assert rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_cuda
+        rows = rows.contiguous()
+        first_row, n_rows, n_list = 0, 0, rows.numel()
+        n = n_list
+        if n_list == 0:                                                     # (an empty tensor has no address, and NULL is the range form)
+            raise ValueError("topk_wide: rows is empty")
+    if excl is not None:
+        assert excl.dtype == torch.int64 and excl_off.dtype == torch.int64 and excl_off.numel() == B + 1
+        excl, excl_off = excl.contiguous(), excl_off.contiguous()
+        if excl.numel() == 0:                                               # every row empty (an empty tensor has no address)
+            excl = excl_off = None
+    fn = lib().rg_topk_wide_workspace
+    fn.restype = ctypes.c_size_t
+    need = int(fn(B, d, c_ll(n), k))
+    ws = _tn_workspace(h.device, need, "topk_wide") if need else None      # 0: unsupported shape -- the call below says which
+    ok = 0 < k <= TOPK_WIDE_MAX_K
+    ids = torch.empty(B, k if ok else 1, device=h.device, dtype=torch.int64)
+    scores = torch.empty(B, k if ok else 1, device=h.device, dtype=torch.float32)
+    a = TopkWideArgs(_p(h), _p(table), first_row, n_rows, _p(rows), n_list, table.shape[0], _p(excl), _p(excl_off), _p(ids), _p(scores),
+                     _p(ws), need, B, d, k)
+    _check(lib().rg_topk_wide(ctypes.byref(a), _full_ce_code(h), _stream()), "rg_topk_wide")
+    return ids, scores
+
+
+def topk_wide_state(device, B):
+    """What the last topk_wide call of B users on the current stream left in its workspace (waits for the stream): the fault word (0 =
+    worked as designed), per user the levels of the radix select that did work and the keys the collect pass kept."""
+    dev = torch.device(device)
+    ws = _TN_WS[("topk_wide", dev.index, torch.cuda.current_stream(dev).cuda_stream)]          # _tn_workspace's key
+    w = ws.view(torch.int32)
+    st = w[64:64 + 8 * B].reshape(B, 8).cpu()
+    return int(w[0].item()), st[:, 5].clone(), st[:, 4].clone()
 
 
 def _i64(t):

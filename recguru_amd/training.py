@@ -373,20 +373,30 @@ def item_list(among, param, domain="a", device=None):
     return _item_list(among, first, n, device)
 
 
+TOPK_NARROW_MAX_K = 128          # hip.topk_scores / hip.topk_list keep k keys per user in LDS; above it recommend takes hip.topk_wide
+
+
 def recommend(model, enc_in, dec_in, k, param, domain="a", device=None, exclude_seen=True, sas=False, among=None):
     """The k items of the whole catalogue that score highest against the last recommender-decoder state: (ids [B, k] int64,
     scores [B, k] f32), score descending, ties by ascending id; with exclude_seen none of the user's own enc_in items.  One pass
     over the item table (hip.topk_scores); [B, vocab] is never formed.  Fewer than k eligible items: -1 / -inf fill the row.
     among (item ids: tensor, array or list; item_list normalises it): the k best of those ids only, the same scores, one pass over
-    the listed rows (hip.topk_list)."""
+    the listed rows (hip.topk_list).  129 <= k <= 1024: the same answer from hip.topk_wide (a few passes, still no [B, vocab]); the
+    first 128 columns equal the k = 128 call's bit for bit.  k > 1024: ValueError."""
     if sas:
         raise NotImplementedError("SASRec scoring is outside the hot path")
     from . import hip
+    if int(k) > hip.TOPK_WIDE_MAX_K:
+        raise ValueError("recommend: k = %d is above the limit of %d items per user" % (int(k), hip.TOPK_WIDE_MAX_K))
     m = _unwrap(model)
     first, n, eos = _catalogue(param, domain)
     rows = None if among is None else item_list(among, param, domain, enc_in.device)
     h = _last_rec_state(model, enc_in, dec_in, domain, param, device)
     excl, off = seen_rows(enc_in, param.pad_index, eos) if exclude_seen else (None, None)
+    if int(k) > TOPK_NARROW_MAX_K:                                # 129 .. 1024: the radix select (hip.topk_wide), either form
+        if rows is not None:
+            return hip.topk_wide(h, ops.shadow(m.item_table(domain)), k, rows=rows, excl=excl, excl_off=off)
+        return hip.topk_wide(h, ops.shadow(m.item_table(domain)), k, first, n, excl=excl, excl_off=off)
     if rows is not None:
         ids, scores, _ = hip.topk_list(h, ops.shadow(m.item_table(domain)), k, rows, excl=excl, excl_off=off)
         return ids, scores
