@@ -417,6 +417,29 @@ int rg_grad_sqnorm_multi(const rg_adam_seg_dev* segs /* device */, int nsegs, fl
  * gives the bits of rg_adam_multi_dev.  nsegs < 1, a null table or weight_decay < 0: RG_ERR_INVALID, nothing launched. */
 int rg_adam_multi_dev2(rg_adam_seg_dev* segs /* device, updated in place */, int nsegs, double lr, double beta1, double beta2,
                        double eps, double weight_decay, int decoupled, const rg_adam_ctl* ctl /* device, may be NULL */, void* stream);
+/* ---- exponential moving average of the weights, kept by the update (csrc/optim.hip) --
+ * rg_adam_multi_dev2 over the same table, and in the same pass, for every element of segment b,
+ *   ema[b][i] <- dt * ema[b][i] + omd * p_new       p_new: the value just stored to segs[b].p[i]
+ *   t = segs[b].step + 1,  d_t = ema_warmup ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay   (double, once per segment)
+ *   dt = (float)d_t,  omd = (float)(1.0 - d_t)
+ * ema is a DEVICE array of nsegs pointers, ema[b] the average of the segs[b].n elements at segs[b].p.  p, m, v and the step counts
+ * get the bits rg_adam_multi_dev2 gives them: one device function holds the update of both.  With ctl->skip set nothing is
+ * written, the average included; the step counts still advance.  The 16-byte route needs p, g, m, v and ema[b] aligned, the scalar
+ * walk serves the rest; both evaluate the same expressions.  ema_decay = 0 makes the average a copy of the weights (dt = 0,
+ * omd = 1).  nsegs < 1, a null table, a null ema, weight_decay < 0 or ema_decay outside 0 <= d < 1 (NaN too): RG_ERR_INVALID,
+ * nothing launched. */
+int rg_adam_multi_dev3(rg_adam_seg_dev* segs /* device, updated in place */, float* const* ema /* device [nsegs] */, int nsegs, double lr,
+                       double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                       const rg_adam_ctl* ctl /* device, may be NULL */, double ema_decay, int ema_warmup, void* stream);
+/* Exchange a[0 .. n) and b[0 .. n) of every pair as raw 32-bit words -- NaN payloads, -0.0 and denormals come through unchanged --
+ * one workgroup per pair (callers split large tensors into chunks, as for the update), 16-byte moves when a and b are both
+ * aligned.  pairs is a DEVICE array.  a and b of a pair must not overlap.  npairs < 1 or a null table: RG_ERR_INVALID, nothing
+ * launched. */
+typedef struct {
+  float* a; float* b;
+  long long n;
+} rg_ema_pair;
+int rg_ema_swap_multi(const rg_ema_pair* pairs /* device */, int npairs, void* stream);
 /* transpose: bit 0 = dst is the transpose of src; bit 1 (RG_CAST_PACK) = dst holds the logical operand M (= src or src^T)
  * [N][K] as consecutive MFMA fragments: block (n / 16, k / 32) = 64 lanes x 8 elements, lane 16 g + i = M[16 nb + i]
  * [32 kb + 8 g .. + 8], blocks ordered nb-major -- a wave's operand fragment is then one contiguous 1 KB (bf16) read.

@@ -16,7 +16,7 @@ import torch
 
 from . import ops, profiling
 from .models import check_recon_handle
-from .optim import Adam, norm_of, options as adam_options
+from .optim import Adam, averaged, has_average, norm_of, options as adam_options
 from .training import TOPK_NARROW_MAX_K, _extend_result, _item_list, _new_result, plot, seen_rows
 
 
@@ -234,7 +234,8 @@ def train(model_train, opt, steps, data, param_config, device_i, neg_sample=True
                 print("BPR loss after %d epochs: %f" % (epoch, loss_epoch))
             plot.plot(param_config.result_path + "/bpr_loss_%s" % param_config.date, loss_epoch)
             if eval_loader is not None:
-                result_tmp = evaluation(model_train, eval_loader, device_i, param_config, k_val=k_val, sas=sas)
+                with averaged(opt):                                  # ema_decay > 0: under the averaged weights; the raw ones are back behind it
+                    result_tmp = evaluation(model_train, eval_loader, device_i, param_config, k_val=k_val, sas=sas)
                 if verbose:
                     print("Freq eval HT@10 %f, test HT@10 %f" % (result_tmp[0]["10"]["ht_eval"][0], result_tmp[0]["10"]["ht_test"][0]))
                     print("Random eval HT@10 %f, test HT@10 %f" % (result_tmp[1]["10"]["ht_eval"][0], result_tmp[1]["10"]["ht_test"][0]))
@@ -272,4 +273,7 @@ def main(args_t, device_t, train_loader_ae, train_loader_re, eval_loader, loader
                          epochs=tune_epochs if tune_epochs is not None else epochs, max_steps=tune_max_steps)
     os.makedirs(os.path.join(args_t.result_path, "model"), exist_ok=True)
     torch.save(MyModel.state_dict(), os.path.join(args_t.result_path, "model/model"))
+    if has_average(opt_rec):                                         # the fine-tuning's average, beside the raw file
+        with averaged(opt_rec):
+            torch.save(MyModel.state_dict(), os.path.join(args_t.result_path, "model/model_ema"))
     return MyModel, pre, tune, result

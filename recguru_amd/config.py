@@ -51,6 +51,8 @@ class get_param(object):
         self.decoupled_wd = bool(_opt(args, "decoupled_wd", False))       # True: AdamW's p *= 1 - lr * wd; False: Adam's g += wd * p
         self.clip_norm = float(_opt(args, "clip_norm", 0.0))              # > 0: global-norm clipping of the reconstruction / recommender steps
         self.skip_nonfinite = bool(_opt(args, "skip_nonfinite", False))   # every optimizer skips a step whose gradient norm is inf / NaN
+        self.ema_decay = float(_opt(args, "ema_decay", 0.0))              # > 0: moving average of the weights; evaluated and saved as <name>_ema
+        self.ema_warmup = bool(_opt(args, "ema_warmup", False))           # True: the decay of step t is min(ema_decay, (1 + t) / (10 + t))
         self.dataset = _DATASETS[self.dataset_pick]
         names = _DOMAINS.get(self.dataset_pick, ("wesee", "txvideo"))
         self.domain_name_a, self.domain_name_b = names

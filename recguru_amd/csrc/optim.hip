@@ -1,6 +1,7 @@
 // Optimizer options on the device-resident segment table of rg_adam_multi_dev (include/recguru_hip.h): the squared global gradient
 // norm with torch.nn.utils.clip_grad_norm_'s coefficient and the non-finite verdict in a control record (rg_grad_sqnorm_multi), and the
-// Adam update that reads that record and applies coupled / decoupled weight decay (rg_adam_multi_dev2).
+// Adam update that reads that record and applies coupled / decoupled weight decay (rg_adam_multi_dev2); the same update keeping an
+// exponential moving average of the weights (rg_adam_multi_dev3) and the exchange of weights and averages (rg_ema_swap_multi).
 //
 // No float atomics and no accumulator shared between workgroups: every sum runs in an order fixed by the table alone, so this unit is
 // compiled once and both libraries get the same bits from it.  The chain of roundings behind total_sq is written out beside
@@ -81,11 +82,14 @@ __global__ __launch_bounds__(OPT_BLOCK) void grad_sqnorm_final_kernel(const floa
   }
 }
 
-// adam_multi_dev_kernel (elementwise.hip) with the clip coefficient, the two decay forms and the skip.  The neutral call
-// (ctl == NULL, wd == 0) takes none of the branches and evaluates that kernel's expressions on the same values.
-__global__ __launch_bounds__(OPT_BLOCK) void adam_multi_dev2_kernel(rg_adam_seg_dev* __restrict__ segs, double lr, double b1d, double b2d,
-                                                                  float eps, float wd, float decay, const rg_adam_ctl* __restrict__ ctl) {
-  const rg_adam_seg_dev sg = segs[blockIdx.x];
+// adam_multi_dev_kernel (elementwise.hip) with the clip coefficient, the two decay forms and the skip: the body of a workgroup's segment,
+// shared by adam_multi_dev2_kernel (EMA = false: e is never touched) and adam_multi_dev3_kernel (EMA = true) so that the two cannot
+// drift.  The neutral call (ctl == NULL, wd == 0) takes none of the branches and evaluates adam_multi_dev_kernel's expressions on the
+// same values.  EMA: behind the update e <- dt * e + omd * p_new on the value just stored to p; the 16-byte route then needs e aligned
+// as well.  Both routes evaluate the same per-element expressions.
+template <bool EMA>
+__device__ __forceinline__ void adam_segment(const rg_adam_seg_dev& sg, float* __restrict__ e, double lr, double b1d, double b2d, float eps,
+                                             float wd, float decay, const rg_adam_ctl* __restrict__ ctl, float dt, float omd) {
   const bool clip = ctl != nullptr;
   const float coef = clip ? ctl->coef : 1.f;
   const bool skip = clip && ctl->skip != 0;
@@ -99,12 +103,18 @@ __global__ __launch_bounds__(OPT_BLOCK) void adam_multi_dev2_kernel(rg_adam_seg_
     const float* __restrict__ g = sg.g;
     float* __restrict__ m = sg.m;
     float* __restrict__ v = sg.v;
-    const long long n4 = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) ? 0 : (sg.n >> 2);
+    const uintptr_t bits = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (EMA ? (uintptr_t)e : (uintptr_t)0);
+    const long long n4 = (bits & 15) ? 0 : (sg.n >> 2);
     for (long long i = threadIdx.x; i < n4; i += OPT_BLOCK) {
       const float4 g4 = reinterpret_cast<const float4*>(g)[i];
       float4 m4 = reinterpret_cast<float4*>(m)[i], v4 = reinterpret_cast<float4*>(v)[i], p4 = reinterpret_cast<float4*>(p)[i];
       float gg[4] = {g4.x, g4.y, g4.z, g4.w};
       float mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w}, pp[4] = {p4.x, p4.y, p4.z, p4.w};
+      float ee[4] = {0.f, 0.f, 0.f, 0.f};
+      if (EMA) {
+        const float4 e4 = reinterpret_cast<float4*>(e)[i];
+        ee[0] = e4.x, ee[1] = e4.y, ee[2] = e4.z, ee[3] = e4.w;
+      }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (clip) gg[j] = coef * gg[j];
@@ -113,10 +123,12 @@ __global__ __launch_bounds__(OPT_BLOCK) void adam_multi_dev2_kernel(rg_adam_seg_
         mm[j] = b1 * mm[j] + (1.f - b1) * gg[j];
         vv[j] = b2 * vv[j] + (1.f - b2) * gg[j] * gg[j];
         pp[j] = pp[j] - step_lr * (mm[j] / (sqrtf(vv[j]) * inv_bc2_sqrt + eps));
+        if (EMA) ee[j] = dt * ee[j] + omd * pp[j];
       }
       reinterpret_cast<float4*>(m)[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
       reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
       reinterpret_cast<float4*>(p)[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
+      if (EMA) reinterpret_cast<float4*>(e)[i] = make_float4(ee[0], ee[1], ee[2], ee[3]);
     }
     for (long long i = (n4 << 2) + threadIdx.x; i < sg.n; i += OPT_BLOCK) {
       float gi = g[i], pi = p[i];
@@ -127,11 +139,56 @@ __global__ __launch_bounds__(OPT_BLOCK) void adam_multi_dev2_kernel(rg_adam_seg_
       const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
       m[i] = mi;
       v[i] = vi;
-      p[i] = pi - step_lr * (mi / (sqrtf(vi) * inv_bc2_sqrt + eps));
+      const float pn = pi - step_lr * (mi / (sqrtf(vi) * inv_bc2_sqrt + eps));
+      p[i] = pn;
+      if (EMA) e[i] = dt * e[i] + omd * pn;
     }
   }
+}
+
+__global__ __launch_bounds__(OPT_BLOCK) void adam_multi_dev2_kernel(rg_adam_seg_dev* __restrict__ segs, double lr, double b1d, double b2d,
+                                                                  float eps, float wd, float decay, const rg_adam_ctl* __restrict__ ctl) {
+  const rg_adam_seg_dev sg = segs[blockIdx.x];
+  adam_segment<false>(sg, nullptr, lr, b1d, b2d, eps, wd, decay, ctl, 0.f, 0.f);
   __syncthreads();                                                 // every thread of the block has read its copy of sg
   if (threadIdx.x == 0) segs[blockIdx.x].step = sg.step + 1;       // a skipped step counts as a step
+}
+
+// adam_multi_dev2_kernel plus the exponential moving average ema[b] of segment b's weights, in the same pass: the new weight is in a
+// register and the skip verdict is at hand.  The decay of this step comes from the segment's own count t = step + 1, in double, once per
+// workgroup: d_t = warmup ? min(decay, (1 + t) / (10 + t)) : decay.  A skipped step leaves the average alone as well.
+__global__ __launch_bounds__(OPT_BLOCK) void adam_multi_dev3_kernel(rg_adam_seg_dev* __restrict__ segs, float* const* __restrict__ ema, double lr,
+                                                                  double b1d, double b2d, float eps, float wd, float decay,
+                                                                  const rg_adam_ctl* __restrict__ ctl, double ema_decay, int ema_warmup) {
+  const rg_adam_seg_dev sg = segs[blockIdx.x];
+  const double t = (double)(sg.step + 1);
+  double d_t = ema_decay;
+  if (ema_warmup) {
+    const double w = (1.0 + t) / (10.0 + t);
+    if (w < d_t) d_t = w;
+  }
+  adam_segment<true>(sg, ema[blockIdx.x], lr, b1d, b2d, eps, wd, decay, ctl, (float)d_t, (float)(1.0 - d_t));
+  __syncthreads();                                                 // every thread of the block has read its copy of sg
+  if (threadIdx.x == 0) segs[blockIdx.x].step = sg.step + 1;       // a skipped step counts as a step
+}
+
+// Exchange the two buffers of a pair as raw 32-bit words (no float ever exists: NaN payloads, -0.0 and denormals come through), one
+// workgroup per pair; 16-byte moves when both buffers are aligned, a word tail behind them, the word walk otherwise.
+__global__ __launch_bounds__(OPT_BLOCK) void ema_swap_kernel(const rg_ema_pair* __restrict__ pairs) {
+  const rg_ema_pair pr = pairs[blockIdx.x];
+  uint32_t* __restrict__ a = reinterpret_cast<uint32_t*>(pr.a);
+  uint32_t* __restrict__ b = reinterpret_cast<uint32_t*>(pr.b);
+  const long long n4 = (((uintptr_t)a | (uintptr_t)b) & 15) ? 0 : (pr.n >> 2);
+  for (long long i = threadIdx.x; i < n4; i += OPT_BLOCK) {
+    const uint4 x = reinterpret_cast<uint4*>(a)[i], y = reinterpret_cast<uint4*>(b)[i];
+    reinterpret_cast<uint4*>(a)[i] = y;
+    reinterpret_cast<uint4*>(b)[i] = x;
+  }
+  for (long long i = (n4 << 2) + threadIdx.x; i < pr.n; i += OPT_BLOCK) {
+    const uint32_t x = a[i], y = b[i];
+    a[i] = y;
+    b[i] = x;
+  }
 }
 
 }  // namespace
@@ -159,6 +216,30 @@ extern "C" int rg_adam_multi_dev2(rg_adam_seg_dev* segs_device, int nsegs, doubl
   const float decay = decoupled ? (float)(1.0 - lr * weight_decay) : 1.f;
   hipLaunchKernelGGL(adam_multi_dev2_kernel, dim3(nsegs), dim3(OPT_BLOCK), 0, (hipStream_t)stream, segs_device, lr, beta1, beta2, (float)eps,
                      wd, decay, ctl);
+  RG_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int rg_adam_multi_dev3(rg_adam_seg_dev* segs_device, float* const* ema_device, int nsegs, double lr, double beta1, double beta2,
+                                  double eps, double weight_decay, int decoupled, const rg_adam_ctl* ctl, double ema_decay, int ema_warmup,
+                                  void* stream) {
+  if (nsegs < 1) return rg_set_error_msg(RG_ERR_INVALID, "adam_multi_dev3: nsegs < 1");
+  if (!segs_device) return rg_set_error_msg(RG_ERR_INVALID, "adam_multi_dev3: null segment table");
+  if (!ema_device) return rg_set_error_msg(RG_ERR_INVALID, "adam_multi_dev3: null average table");
+  if (!(weight_decay >= 0.0)) return rg_set_error_msg(RG_ERR_INVALID, "adam_multi_dev3: weight_decay < 0");
+  if (!(ema_decay >= 0.0 && ema_decay < 1.0)) return rg_set_error_msg(RG_ERR_INVALID, "adam_multi_dev3: ema_decay outside [0, 1)");
+  const float wd = decoupled ? 0.f : (float)weight_decay;
+  const float decay = decoupled ? (float)(1.0 - lr * weight_decay) : 1.f;
+  hipLaunchKernelGGL(adam_multi_dev3_kernel, dim3(nsegs), dim3(OPT_BLOCK), 0, (hipStream_t)stream, segs_device, ema_device, lr, beta1, beta2,
+                     (float)eps, wd, decay, ctl, ema_decay, ema_warmup);
+  RG_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int rg_ema_swap_multi(const rg_ema_pair* pairs_device, int npairs, void* stream) {
+  if (npairs < 1) return rg_set_error_msg(RG_ERR_INVALID, "ema_swap_multi: npairs < 1");
+  if (!pairs_device) return rg_set_error_msg(RG_ERR_INVALID, "ema_swap_multi: null pair table");
+  hipLaunchKernelGGL(ema_swap_kernel, dim3(npairs), dim3(OPT_BLOCK), 0, (hipStream_t)stream, pairs_device);
   RG_CHECK_LAUNCH();
   return 0;
 }

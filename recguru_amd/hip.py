@@ -112,7 +112,7 @@ SYMBOLS = ["rg_last_error", "rg_version", "rg_gemm_nt", "rg_gemm_tn", "rg_attn_f
            "rg_shared_ce_supported", "rg_shared_ce_bwd_workspace", "rg_shared_ce_fwd", "rg_shared_ce_bwd",
            "rg_topk_workspace", "rg_topk_scores", "rg_topk_list_workspace", "rg_topk_list",
            "rg_topk_wide_workspace", "rg_topk_wide",
-           "rg_grad_sqnorm_multi", "rg_adam_multi_dev2",
+           "rg_grad_sqnorm_multi", "rg_adam_multi_dev2", "rg_adam_multi_dev3", "rg_ema_swap_multi",
            "rg_pos_grad_workspace", "rg_pos_grad",
            "rg_attn_probs", "rg_attn_cross_probs", "rg_attn_rollout"]
 LOSS_SAMPLED_CE, LOSS_BPR, LOSS_BPR_SAS = 0, 1, 2
@@ -951,6 +951,25 @@ def adam_multi_dev2(seg_table_dev, nsegs, lr, beta1, beta2, eps, weight_decay=0.
     coupled (torch.optim.Adam) / decoupled (torch.optim.AdamW) weight decay."""
     _check(lib().rg_adam_multi_dev2(_vp(seg_table_dev), int(nsegs), c_d(lr), c_d(beta1), c_d(beta2), c_d(eps), c_d(weight_decay),
                                     int(bool(decoupled)), _vp(ctl), _stream()), "rg_adam_multi_dev2")
+
+
+# numpy mirror of rg_ema_pair (24 bytes: 2 pointers, n)
+EMA_PAIR_DTYPE = [("a", "<u8"), ("b", "<u8"), ("n", "<i8")]
+
+
+def adam_multi_dev3(seg_table_dev, ema_ptrs_dev, nsegs, lr, beta1, beta2, eps, weight_decay=0.0, decoupled=False, ctl=None,
+                    ema_decay=0.0, ema_warmup=False):
+    """adam_multi_dev2 that also keeps the exponential moving average of the weights: ema_ptrs_dev is a uint8 CUDA tensor holding nsegs
+    device pointers, the average of each segment.  e <- dt * e + omd * p_new with d_t = min(ema_decay, (1 + t) / (10 + t)) under
+    ema_warmup (t: the segment's step count after this update), ema_decay otherwise; a skipped step leaves the average alone."""
+    _check(lib().rg_adam_multi_dev3(_vp(seg_table_dev), _vp(ema_ptrs_dev), int(nsegs), c_d(lr), c_d(beta1), c_d(beta2), c_d(eps),
+                                    c_d(weight_decay), int(bool(decoupled)), _vp(ctl), c_d(ema_decay), int(bool(ema_warmup)), _stream()),
+           "rg_adam_multi_dev3")
+
+
+def ema_swap_multi(pair_table_dev, npairs):
+    """pair_table_dev: uint8 CUDA tensor holding npairs rg_ema_pair records; the two buffers of every pair change places, word for word."""
+    _check(lib().rg_ema_swap_multi(_vp(pair_table_dev), int(npairs), _stream()), "rg_ema_swap_multi")
 
 
 CAST_SEG_DTYPE = [("src", "<u8"), ("dst", "<u8"), ("R", "<i4"), ("C", "<i4"), ("ld", "<i4"), ("row_off", "<i4"),
@@ -2001,7 +2020,7 @@ def _work_shared_ce_dw(h, table_rows, labels, cand, mask, live, wc, lse, coef_po
 _WORK = {"full_ce_fwd": _work_full_ce_fwd, "full_ce_dw": _work_full_ce_dw, "shared_ce_fwd": _work_shared_ce_fwd, "shared_ce_dw": _work_shared_ce_dw, "attn_out_bwd": _work_attn_out_bwd, "attn_out_bwd_cross": _work_attn_out_bwd_cross, "ln_bwd": _work_ln_bwd, "gemm_tn_layer": _work_gemm_tn_layer, "item_loss_scatter_binned": _work_item_loss_scatter, "attn_lastq_x_fwd": _work_lastq_x_fwd, "attn_lastq_x_bwd": _work_lastq_x_bwd, "item_loss_train": _work_item_loss_train,
          "ffn_bwd_data": _work_ffn_bwd, "attn_fwd_x": _work_attn_fwd_x, "post_attn_fwd": _work_post_attn, "gemm_nt": _work_gemm_nt, "gemm_tn": _work_gemm_tn, "attn_fwd": _work_attn_fwd, "attn_bwd": _work_attn_bwd,
          "embed_pe_fwd": _work_embed_fwd, "item_loss_fwd": _work_item_loss, "item_loss_bwd": _work_item_loss}
-_PLAIN = ["dropout_", "cross_rows", "adam_multi", "adam_multi_dev", "adam_multi_dev2", "grad_sqnorm_multi", "disc_rows", "item_loss_bwd_binned", "embed_scatter_bwd", "bcast_add_ln", "seq_sum", "colsum", "outer_posmask", "interpolate",
+_PLAIN = ["dropout_", "cross_rows", "adam_multi", "adam_multi_dev", "adam_multi_dev2", "adam_multi_dev3", "ema_swap_multi", "grad_sqnorm_multi", "disc_rows", "item_loss_bwd_binned", "embed_scatter_bwd", "bcast_add_ln", "seq_sum", "colsum", "outer_posmask", "interpolate",
           "gp_penalty", "sum_into", "adam", "cast", "attn_lastq_fwd", "attn_lastq_bwd", "cross_drop_scale", "seq_wsum",
           "embed_scatter_bwd_binned", "scale_dev", "dropout_gelu", "add_drop_ln", "mse", "cross_add_ln",
           "attn_probs", "attn_cross_probs", "attn_rollout"]

@@ -19,7 +19,7 @@ import torch
 
 from . import ops, profiling
 from .models import check_recon_handle
-from .optim import Adam, norm_of, options as adam_options
+from .optim import Adam, averaged, has_average, norm_of, options as adam_options
 
 LAMBDA = .1         # gan_training.py:21
 CRITIC_ITERS = 5    # gan_training.py:22
@@ -699,12 +699,13 @@ def train_gan_all(netG, netD, gan_loader, opt_d, opt_g, device, param, iteration
         prof.end(phase)
         if iteration > int(iterations * 0.8) and iteration % 30 == 29 and (evaluate is not None or test_loaders is not None):
             netG.eval()                          # gan_training.py:570-580
-            if evaluate is not None:
-                evaluate(netG)
-            else:
-                _extend_result(result, evaluation_2(netG, test_loaders, device, param, k_val=k_val, sas=False,
-                                                    domain=domain))
-                _dump_result(result, os.path.join(param.result_path, "result_%s.pickle" % param.target_domain), dp)
+            with averaged(opt_final_rec):        # param.ema_decay > 0: the snapshot is the average of phase 3's iterates, not the last one
+                if evaluate is not None:
+                    evaluate(netG)
+                else:
+                    _extend_result(result, evaluation_2(netG, test_loaders, device, param, k_val=k_val, sas=False,
+                                                        domain=domain))
+                    _dump_result(result, os.path.join(param.result_path, "result_%s.pickle" % param.target_domain), dp)
             netG.train()
         if iteration % 100 == 99 and dp.rank == 0 and os.path.isdir(param.result_path):     # :583-586
             os.makedirs(os.path.join(param.result_path, "gan_loss"), exist_ok=True)
@@ -747,7 +748,8 @@ def recommendation_tune(model, rec_loader, test_loader, steps, param, device, do
             if norm_of(opt) is not None:
                 plot.plot(param.result_path + "/grad_norm_tune_%s" % domain, float(norm_of(opt)))
             if test_loader is not None:
-                result_tmp = evaluation_2(model, test_loader, device, param, k_val=k_val, sas=False, domain=domain)
+                with averaged(opt):             # param.ema_decay > 0: under the averaged weights; the raw ones are back behind it
+                    result_tmp = evaluation_2(model, test_loader, device, param, k_val=k_val, sas=False, domain=domain)
                 print("eval HT@10 %f, test HT@10 %f" % (result_tmp[0]["10"]["ht_eval"][0], result_tmp[0]["10"]["ht_test"][0]))
                 print("eval HT@10 %f, test HT@10 %f" % (result_tmp[1]["10"]["ht_eval"][0], result_tmp[1]["10"]["ht_test"][0]))
                 _extend_result(result, result_tmp)
@@ -767,6 +769,9 @@ def main_2(auto_cross, opt_rec, netD, opt_gen, opt_dis, param, device_t, ae_load
                   loss_type="s_soft", opt_type="schedule", dp=dp)
     if dp is None or dp.rank == 0:
         torch.save(_unwrap(auto_cross).state_dict(), os.path.join(param.model_path, "pre_model"))
+        if has_average(opt_rec):                 # the same weights' average over phase 1, beside the raw file
+            with averaged(opt_rec):
+                torch.save(_unwrap(auto_cross).state_dict(), os.path.join(param.model_path, "pre_model_ema"))
     print("============ Adversarial and recommendation training (phase 2 and phase 3).")
     return train_gan_all(auto_cross, netD, ae_loaders, opt_dis, opt_gen, device_t, param, param.training_steps_tune,
                          train_overlap, rec_loaders, test_loaders, domain=param.target_domain, overlap=False, dp=dp)

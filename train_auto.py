@@ -58,6 +58,11 @@ def parse():
     p.add_argument("--clip_norm", type=float, default=0.0, help="global gradient-norm bound of both optimizers (clip_grad_norm_ semantics); 0 = off")
     p.add_argument("--skip_nonfinite", type=lambda v: v == "True", default=False,
                    help="True: skip a step whose gradient norm is inf or NaN (decided on the device, no host wait)")
+    p.add_argument("--ema_decay", type=float, default=0.0,
+                   help="decay of an exponential moving average of the weights kept by both optimizers: evaluations run under the "
+                        "averaged weights and model/model_ema is saved beside model/model; 0 = off")
+    p.add_argument("--ema_warmup", type=lambda v: v == "True", default=False,
+                   help="True: the average's decay at a parameter's step t is min(ema_decay, (1 + t) / (10 + t))")
     p.add_argument("--epochs", type=int, default=500, help="epochs per stage (train_auto.py:101 hard-codes 500)")
     p.add_argument("--steps", type=int, default=200, help="pre-training steps")
     p.add_argument("--tune_steps", type=int, default=100, help="BPR fine-tuning steps")

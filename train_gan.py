@@ -71,6 +71,11 @@ def parse():
                    help="global gradient-norm bound of the reconstruction / recommender steps (clip_grad_norm_ semantics); 0 = off")
     p.add_argument("--skip_nonfinite", type=str2bool_par, default=False,
                    help="True: every optimizer skips a step whose gradient norm is inf or NaN (decided on the device, no host wait)")
+    p.add_argument("--ema_decay", type=float, default=0.0,
+                   help="decay of an exponential moving average of the weights kept by the reconstruction / recommender optimizers: "
+                        "evaluations run under the averaged weights and <name>_ema is saved beside every weight file; 0 = off")
+    p.add_argument("--ema_warmup", type=str2bool_par, default=False,
+                   help="True: the average's decay at a parameter's step t is min(ema_decay, (1 + t) / (10 + t))")
     return p.parse_args()
 
 
