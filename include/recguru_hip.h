@@ -749,6 +749,43 @@ typedef struct {
 size_t rg_topk_wide_workspace(int B, int d, long long n_rows, int K);   /* n_rows: or n_list; 0 = unsupported shape */
 int rg_topk_wide(const rg_topk_wide_args* args /* host */, int dtype, void* stream);
 
+/* ---- hard negatives: each position's top-scoring ids of one sampled pool (csrc/hard_negs.hip) ----------------
+ * The training form of the list walk of rg_topk_list.  For every position t with mask[t] != 0, in sequence b = t / L:
+ *   E_t    the pool ids c with c != labels[t] and c not in excl[excl_lo[b] .. excl_hi[b]) (a sorted run of unique ids; excl NULL: no
+ *          run), ordered by the key of the calls above: score(h_t, table[c]) descending, ties by ascending id.  Same score function:
+ *          a (h row, table row) pair has the same bits here as in rg_topk_scores / rg_topk_list, whatever n, L, the tile or the pool.
+ *   out    for j < k: if skip + j < |E_t|, out[t * ld_out + j] = the (skip + j)-th id of that order and out_scores[t * k + j] its
+ *          score; otherwise the out slot is LEFT AS IT WAS (the caller pre-fills [n, ld_out] with its private random draw) and the
+ *          out_scores slot is -inf.  Positions with mask == 0 and columns >= k are never written; positions with mask == 0 are not
+ *          scored.  Nothing of size [n, C] is stored; there is no workspace but one 64-bit word for the check below.
+ *   skip   drops that many ids from the head of the order (the hardest members of a large pool are often unlabelled positives).
+ *   checked = 1: the caller vouches for pool (strictly ascending, inside [0, table_rows)); the call enqueues and returns -- no
+ *          copy-back, no wait.  A pool id outside [0, table_rows) is still never dereferenced: it is ineligible.
+ *   checked = 0: pool is verified on the device first; one word is copied back and the stream waited for.  RG_ERR_INVALID names the
+ *          first offending position and its value; nothing is scored and nothing is written.
+ * One wave per live 16-position tile (live16 = rg_live_tiles(mask, n)), one pass, one launch; no float atomics -- the same code in
+ * the deterministic library, bit-identical across repeats, batch splits and tile placements.
+ * Refusals, all before any launch.  RG_ERR_UNSUPPORTED: d not in {64, 128, 256}; dtype other than RG_BF16 / RG_X3; k < 1; skip < 0;
+ * skip + k > 128; C < 1 or >= 2^31; table_rows or n >= 2^31.  RG_ERR_INVALID: L < 1; n % L != 0; ld_out < k; a missing buffer (h,
+ * table, pool, labels, mask, live16, out); excl without both offset arrays.  n == 0 is a no-op. */
+typedef struct {
+  const void* h;            /* [n, d] decoder states, operand dtype */
+  const void* table;        /* [table_rows, d] operand dtype */
+  long long table_rows;
+  const int64_t* pool;      /* [C] strictly ascending table rows, one pool for the whole call */
+  long long C;
+  const int64_t* labels;    /* [n] each position's own target: never returned for that position */
+  const float* mask;        /* [n]; positions with mask == 0 are not scored and not written */
+  const int* live16;        /* rg_live_tiles(mask, n) */
+  const int64_t* excl;      /* sorted unique ids per sequence, or NULL */
+  const int64_t* excl_lo;   /* [n / L] start of sequence b's row in excl */
+  const int64_t* excl_hi;   /* [n / L] end (exclusive) */
+  int64_t* out;             /* [n, ld_out]: columns 0 .. k-1 receive ids */
+  float* out_scores;        /* [n, k] or NULL */
+  long long n; int L, d, k, skip, ld_out, checked;
+} rg_hard_negs_args;
+int rg_hard_negs(const rg_hard_negs_args* args /* host */, int dtype, void* stream);
+
 /* ---- fused post-attention block, forward -------------------------------------------------------------
  * y = LN(ctx.Wo^T + bo + x) [; y = LN(y + o_bcast[b])] ; out = LN(gelu(y.W1^T + b1).W2^T + b2 + y) * rowmask
  * = MultiHeadAttention tail (Transformer/transformer.py:160-161) [+ collapsed dec_enc_attn, :259, Q1]

@@ -45,6 +45,9 @@ class get_param(object):
         self.rs_d_model, self.rs_num_blocks, self.rs_d_ff = args.d_model, self.num_blocks, args.d_ff
         self.n_negs = args.n_negs
         self.shared_negs = int(_opt(args, "shared_negs", 0))       # > 0: one shared candidate list per reconstruction batch
+        self.hard_negs = int(_opt(args, "hard_negs", 0))           # > 0: hard negatives, the size of the pool drawn per batch; 0 = off
+        self.hard_k = int(_opt(args, "hard_k", 0))                 # how many of a position's negatives are hard ones; 0 = all of them
+        self.hard_skip = int(_opt(args, "hard_skip", 0))           # ranks dropped from the head of the pool's order
         self.pos_train = bool(_opt(args, "pos_train", False))      # True: learned positional table (blocks.PositionalEncodingM) instead of the sinusoid
         # optimizer options (recguru_amd/optim.py), all neutral by default: the reference configures none of them
         self.weight_decay = float(_opt(args, "weight_decay", 0.0))
@@ -131,3 +134,22 @@ class get_param(object):
         self.smoothing = 0.1
         self.dis_dim = self.d_model * 5
         self.training_steps_tune = int(_opt(args, "steps_tune", 300))   # ":237  # for testing"
+
+
+def hard_negs_options(param, k=None):
+    """The loaders' hard-negative arguments of a run (--hard_negs / --hard_k / --hard_skip): {} when the feature is off, else the
+    keywords of sampler.DeviceLoader / data.device_loader_gen.  k: the negatives per position of the loader they go to -- the phases
+    differ (n_negs, n_bpr_neg), and a --hard_k above a phase's k means all of that phase's.  ValueError where the run has no
+    per-position negatives to harden."""
+    if param.hard_negs <= 0:
+        return {}
+    if param.shared_negs > 0:
+        raise ValueError("--hard_negs and --shared_negs exclude each other: a shared candidate list has no per-position negatives")
+    if not param.decoder_neg:
+        raise ValueError("--hard_negs needs sampled negatives (decoder_neg=True): the full-catalogue loss has none")
+    if param.hard_k < 0 or param.hard_skip < 0:
+        raise ValueError("--hard_k and --hard_skip must not be negative")
+    hard_k = param.hard_k or None
+    if k is not None and hard_k is not None and hard_k > k:
+        hard_k = None
+    return {"hard_negs": param.hard_negs, "hard_k": hard_k, "hard_skip": param.hard_skip}

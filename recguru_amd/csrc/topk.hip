@@ -34,7 +34,7 @@
 #include <vector>
 
 #include "rg_common.hip.h"
-#include "topk_common.hip.h"          // tk_scores(), the key, the row / user loads, tk_excluded, the list helpers, tk_slices: shared with topk_wide.hip
+#include "topk_common.hip.h"          // tk_scores(), the key, the row / user loads, tk_excluded, tk_insert, the list helpers, tk_slices: shared with topk_wide.hip and hard_negs.hip
 #include "../../include/recguru_hip.h"
 
 namespace {
@@ -104,28 +104,6 @@ __global__ __launch_bounds__(TK_THREADS) void tk_gather_kernel(rg_topk_args a, c
 // ------------------------------------------------------------------------------------------------
 // the pass over the catalogue
 // ------------------------------------------------------------------------------------------------
-// one key into user list lst[0, K): nothing if it does not beat the worst kept key, else it replaces it (wave-uniform arguments)
-__device__ __forceinline__ void tk_insert(volatile tk_key* lst, int K, volatile tk_key* thr, volatile int* wpos, tk_key ck, int lane) {
-  if (ck <= *thr) return;
-  const int p = *wpos;
-  if (lane == 0) lst[p] = ck;
-  __builtin_amdgcn_wave_barrier();
-  tk_key w = ~0ull;
-  int wp = 0;
-  for (int e = lane; e < K; e += RG_WAVE) {
-    const tk_key v = lst[e];
-    if (v < w) { w = v; wp = e; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const tk_key ow = tk_shfl_xor(w, o);
-    const int op = __shfl_xor(wp, o);
-    if (ow < w || (ow == w && op < wp)) { w = ow; wp = op; }
-  }
-  if (lane == 0) { *thr = w; *wpos = wp; }
-  __builtin_amdgcn_wave_barrier();
-}
-
 template <typename T, int D, bool LIST>
 __global__ __launch_bounds__(TK_THREADS) void tk_main_kernel(rg_topk_args a, const int64_t* __restrict__ rows, const float* __restrict__ tscore,
                                                              tk_key* __restrict__ part, long long tiles_per_slice) {

@@ -84,6 +84,28 @@ __device__ __forceinline__ bool tk_excluded(const int64_t* __restrict__ ex, long
   return lo < end && ex[lo] == id;
 }
 
+// one key into user list lst[0, K): nothing if it does not beat the worst kept key, else it replaces it (wave-uniform arguments)
+__device__ __forceinline__ void tk_insert(volatile tk_key* lst, int K, volatile tk_key* thr, volatile int* wpos, tk_key ck, int lane) {
+  if (ck <= *thr) return;
+  const int p = *wpos;
+  if (lane == 0) lst[p] = ck;
+  __builtin_amdgcn_wave_barrier();
+  tk_key w = ~0ull;
+  int wp = 0;
+  for (int e = lane; e < K; e += RG_WAVE) {
+    const tk_key v = lst[e];
+    if (v < w) { w = v; wp = e; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const tk_key ow = tk_shfl_xor(w, o);
+    const int op = __shfl_xor(wp, o);
+    if (ow < w || (ow == w && op < wp)) { w = ow; wp = op; }
+  }
+  if (lane == 0) { *thr = w; *wpos = wp; }
+  __builtin_amdgcn_wave_barrier();
+}
+
 // table row at position pos of the list (-1 past its end)
 __device__ __forceinline__ int tk_list_id(const int64_t* __restrict__ rows, unsigned int pos, unsigned int n) {
   return pos < n ? (int)rows[pos] : -1;                         // (table_rows < 2^31: one register)

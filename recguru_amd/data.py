@@ -58,10 +58,11 @@ def domain_from_pickles(files, L, eos, V, k, seed=0, wf=None):
 
 
 def device_loader_gen(files, param, num_n, domain="a", device="cuda", rank=0, world=1, seed=0, wf=None, batch_size=None,
-                      eval_n=False, rec=False, exclude_val=False, shared_negs=0):
+                      eval_n=False, rec=False, exclude_val=False, shared_negs=0, hard_negs=0, hard_k=None, hard_skip=0):
     """dataloader_gen on the device: the pickles' users go to the GPU as CSR rows once; every batch
     is assembled (seq_padding) and gets FRESH negatives (enc_maxlen * num_n per user, or candidate_size with eval_n)
-    by two kernel launches -- recguru_amd.sampler.  shared_negs > 0: one candidate list per batch instead (DeviceLoader)."""
+    by two kernel launches -- recguru_amd.sampler.  shared_negs > 0: one candidate list per batch instead (DeviceLoader);
+    hard_negs > 0: the draws plus one scored pool per batch (models.HardNegatives)."""
     from .sampler import DeviceDomain, DeviceLoader
     eos = param.vocab_size_a if domain == "a" else param.vocab_size_b
     seqs, val, test = [], [], []
@@ -73,7 +74,8 @@ def device_loader_gen(files, param, num_n, domain="a", device="cuda", rank=0, wo
     dom = DeviceDomain(seqs, val, test, eos - 1, device, exclude_val=exclude_val, wf=wf)
     n_neg = param.candidate_size if eval_n else param.enc_maxlen * num_n
     return DeviceLoader(dom, batch_size or param.batch_size, param.enc_maxlen, param.rec_maxlen if rec else param.enc_maxlen,
-                        eos, n_neg, seed=seed, shuffle=True, rank=rank, world=world, shared_negs=shared_negs)
+                        eos, n_neg, seed=seed, shuffle=True, rank=rank, world=world, shared_negs=shared_negs,
+                        hard_negs=hard_negs, hard_k=hard_k, hard_skip=hard_skip)
 
 
 def users_from_pickles(files):

@@ -111,7 +111,7 @@ SYMBOLS = ["rg_last_error", "rg_version", "rg_gemm_nt", "rg_gemm_tn", "rg_attn_f
            "rg_full_ce_supported", "rg_full_ce_fwd", "rg_full_ce_dw",
            "rg_shared_ce_supported", "rg_shared_ce_bwd_workspace", "rg_shared_ce_fwd", "rg_shared_ce_bwd",
            "rg_topk_workspace", "rg_topk_scores", "rg_topk_list_workspace", "rg_topk_list",
-           "rg_topk_wide_workspace", "rg_topk_wide",
+           "rg_topk_wide_workspace", "rg_topk_wide", "rg_hard_negs",
            "rg_grad_sqnorm_multi", "rg_adam_multi_dev2", "rg_adam_multi_dev3", "rg_ema_swap_multi",
            "rg_pos_grad_workspace", "rg_pos_grad",
            "rg_attn_probs", "rg_attn_cross_probs", "rg_attn_rollout"]
@@ -1171,6 +1171,49 @@ def topk_wide_state(device, B):
     w = ws.view(torch.int32)
     st = w[64:64 + 8 * B].reshape(B, 8).cpu()
     return int(w[0].item()), st[:, 5].clone(), st[:, 4].clone()
+
+
+class HardNegsArgs(ctypes.Structure):
+    _fields_ = [("h", c_p), ("table", c_p), ("table_rows", c_ll), ("pool", c_p), ("C", c_ll), ("labels", c_p), ("mask", c_p),
+                ("live16", c_p), ("excl", c_p), ("excl_lo", c_p), ("excl_hi", c_p), ("out", c_p), ("out_scores", c_p),
+                ("n", c_ll), ("L", c_i), ("d", c_i), ("k", c_i), ("skip", c_i), ("ld_out", c_i), ("checked", c_i)]
+
+
+def hard_negs(h, table, pool, labels, mask, L, k, skip=0, excl=None, excl_lo=None, excl_hi=None, out=None, checked=False,
+              want_scores=False):
+    """Each live position's hard negatives among pool [C] int64, strictly ascending table rows shared by the call (rg_hard_negs;
+    nothing of size [n, C] is stored): (out, scores [n,k] f32 | None).  For position t of sequence t // L with mask != 0, columns
+    0 .. k-1 of out [n, ld_out >= k] int64 receive ranks skip .. skip + k - 1 of the pool ids other than labels[t] and outside
+    excl[excl_lo[t // L] : excl_hi[t // L]] (sorted unique ids), score descending, ties by ascending id; a slot the position has no
+    id for, every column >= k and every position with mask == 0 keep what out held (scores: -inf in such a slot of a live position).
+    out defaults to a fresh [n, k] of -1 (tests and inspection; training passes its pre-filled private draw).  checked=True: the
+    caller vouches for pool and the call enqueues without a wait; otherwise pool is verified on the device (one word copied back)."""
+    n, d = h.shape
+    k, skip, L = int(k), int(skip), int(L)
+    assert h.is_contiguous() and table.is_contiguous() and table.dtype == h.dtype and table.shape[1] == d
+    assert pool.dtype == torch.int64 and pool.dim() == 1 and pool.is_cuda
+    assert labels.dtype == torch.int64 and labels.numel() == n and mask.dtype == torch.float32 and mask.numel() == n
+    assert (excl_lo is None) == (excl_hi is None) and (excl is not None or excl_lo is None)
+    pool, labels, mask = pool.contiguous(), labels.contiguous().view(-1), mask.contiguous().view(-1)
+    if excl is not None:
+        assert excl.dtype == torch.int64 and excl.is_contiguous()
+        for o in (excl_lo, excl_hi):
+            assert o is None or (o.dtype == torch.int64 and o.numel() * max(L, 1) == n)
+        if excl_lo is not None:
+            excl_lo, excl_hi = excl_lo.contiguous(), excl_hi.contiguous()
+        if excl.numel() == 0 and excl_lo is not None:                       # every row empty (an empty tensor has no address)
+            excl = excl_lo = excl_hi = None
+    if out is None:
+        out = torch.full((n, max(k, 1)), -1, device=h.device, dtype=torch.int64)
+    assert out.dtype == torch.int64 and out.is_cuda and out.dim() == 2 and out.shape[0] == n and (n == 0 or out.stride(1) == 1)
+    scores = torch.full((n, max(k, 1)), float("-inf"), device=h.device, dtype=torch.float32) if want_scores else None
+    live = live_tiles(mask, n) if n else None
+    C = pool.numel()
+    a = HardNegsArgs(_p(h) if n else None, _p(table), table.shape[0], _p(pool) if C else None, C, _p(labels) if n else None,
+                     _p(mask) if n else None, _p(live), _p(excl), _p(excl_lo), _p(excl_hi), _p(out) if n else None, _p(scores) if n else None,
+                     n, L, d, k, skip, out.stride(0) if n else max(k, 1), int(bool(checked)))
+    _check(lib().rg_hard_negs(ctypes.byref(a), _full_ce_code(h), _stream()), "rg_hard_negs")
+    return out, scores
 
 
 def _i64(t):

@@ -27,14 +27,21 @@ def _f32_mask(ids, pad):
 
 class SampledLogits(object):
     """Deferred logits of the positive + k sampled negatives per position
-    (AutoEnc4Rec_cross.py:201-215).  Holds the decoder states and the item ids."""
+    (AutoEnc4Rec_cross.py:201-215).  Holds the decoder states and the item ids.  neg may be a HardNegatives: it becomes the [n, k] ids
+    when a loss is asked for, under that loss's mask (resolve_negatives: the positions the loss counts are the ones that are scored)."""
 
     def __init__(self, h, table, pos, neg, k, skip_row=-1):
         self.h, self.table, self.pos, self.neg, self.k, self.skip_row = h, table, pos, neg, k, skip_row
 
+    def negatives(self, mask=None):
+        """The [n, k] negative ids the losses see (mask None: every position counts, what dense() shows)."""
+        if isinstance(self.neg, HardNegatives) and mask is None:
+            mask = torch.ones(self.pos.numel(), device=self.h.device, dtype=torch.float32)
+        return resolve_negatives(self.h, self.table, self.pos, self.neg, self.k, mask)
+
     def loss(self, mask):
         """SampledCrossEntropyLoss with label 0 and masked mean (tools/lossfunctions.py:36-49)."""
-        return ops.sampled_softmax_loss(self.h, self.table, self.pos, self.neg, mask, self.k, self.skip_row)
+        return ops.sampled_softmax_loss(self.h, self.table, self.pos, self.negatives(mask), mask, self.k, self.skip_row)
 
     def dense(self):
         """The [B, L, 1 + k] logits tensor the reference's forward returns (AutoEnc4Rec_cross.py:211-215: column 0 the
@@ -44,12 +51,12 @@ class SampledLogits(object):
         d = self.h.shape[-1]
         h2 = self.h.detach().contiguous().view(-1, d)
         scores, _ = hip.rank_scores(h2, ops.shadow(self.table), self.pos.contiguous().view(-1),
-                                    self.neg.contiguous().view(-1, self.k), want_rank=False)
+                                    self.negatives().contiguous().view(-1, self.k), want_rank=False)
         return scores.view(tuple(self.h.shape[:-1]) + (self.k + 1,))
 
     def bpr(self, mask, sas=False):
         """BPRLoss (tools/lossfunctions.py:56-72); sas=True: BPRLoss_sas (:79-96), what train_auto.py uses (:26)."""
-        return ops.bpr_loss(self.h, self.table, self.pos, self.neg, mask, self.k, self.skip_row, sas=sas)
+        return ops.bpr_loss(self.h, self.table, self.pos, self.negatives(mask), mask, self.k, self.skip_row, sas=sas)
 
 
 class SharedLogits(object):
@@ -80,6 +87,56 @@ class SharedLogits(object):
     def bpr(self, mask, sas=False):
         raise NotImplementedError("BPR takes per-position negatives (a 2-D n_items): a shared candidate list serves the sampled "
                                   "softmax loss only")
+
+
+class HardNegatives(object):
+    """A value for the n_items argument: per-position negatives whose first k_hard columns are the positions' HARD negatives -- ranks
+    skip .. skip + k_hard - 1 of one sampled pool under the current model (hip.hard_negs) -- and whose other columns, and
+    every slot the pool has no id for, are the ordinary private draw.  private: [B, L * k] (what the loaders yield); pool: 1-D, strictly
+    ascending table rows; excl / excl_lo / excl_hi: each sequence's sorted exclusion row excl[excl_lo[b] : excl_hi[b]], or None."""
+
+    def __init__(self, private, pool, k_hard, skip=0, excl=None, excl_lo=None, excl_hi=None):
+        if not torch.is_tensor(private) or private.dtype != torch.int64 or private.dim() != 2:
+            raise ValueError("HardNegatives: private must be the [B, L * k] int64 draw")
+        if not torch.is_tensor(pool) or pool.dtype != torch.int64 or pool.dim() != 1 or pool.numel() < 1:
+            raise ValueError("HardNegatives: pool must be a non-empty 1-D int64 list of table rows")
+        if int(k_hard) < 1:
+            raise ValueError("HardNegatives: k_hard must be at least 1 (got %d)" % int(k_hard))
+        if int(skip) < 0:
+            raise ValueError("HardNegatives: skip must not be negative (got %d)" % int(skip))
+        if (excl_lo is None) != (excl_hi is None) or (excl is None) != (excl_lo is None):
+            raise ValueError("HardNegatives: excl, excl_lo and excl_hi come together")
+        if excl_lo is not None and (excl_lo.numel() != private.shape[0] or excl_hi.numel() != private.shape[0]):
+            raise ValueError("HardNegatives: excl_lo / excl_hi need one entry per sequence (%d)" % private.shape[0])
+        self.private, self.pool, self.k_hard, self.skip = private, pool, int(k_hard), int(skip)
+        self.excl, self.excl_lo, self.excl_hi = excl, excl_lo, excl_hi
+
+    def to(self, device):
+        """The loaders' `n_items.to(device)` (get_next_batch): every tensor moved, the exclusion values shared when already there."""
+        mv = lambda t: None if t is None else t.to(device)
+        return HardNegatives(mv(self.private), mv(self.pool), self.k_hard, self.skip, mv(self.excl), mv(self.excl_lo), mv(self.excl_hi))
+
+
+def resolve_negatives(h, table, labels, n_items, k, mask):
+    """n_items as the item-loss kernels take it.  A plain tensor passes through untouched.  A HardNegatives becomes a fresh [n, k]
+    buffer: the private draw, its first k_hard columns overwritten by each live position's hard negatives of the pool, scored with
+    the detached decoder states h against the operand-tier copy of table -- no gradient flows through the selection."""
+    if not isinstance(n_items, HardNegatives):
+        return n_items
+    from . import hip
+    hn, k = n_items, int(k)
+    if not 1 <= hn.k_hard <= k:
+        raise ValueError("HardNegatives: need 1 <= k_hard <= k (k_hard=%d, k=%d)" % (hn.k_hard, k))
+    d = h.shape[-1]
+    h2 = h.detach().contiguous().view(-1, d)
+    n = h2.shape[0]
+    B = hn.private.shape[0]
+    if hn.private.numel() != n * k or n % B != 0:
+        raise ValueError("HardNegatives: private holds %d ids, %d positions x k=%d need %d" % (hn.private.numel(), n, k, n * k))
+    neg = hn.private.reshape(n, k).clone()
+    hip.hard_negs(h2, ops.shadow(table), hn.pool, labels.contiguous().view(-1), mask.reshape(-1).contiguous(), n // B, hn.k_hard,
+                  skip=hn.skip, excl=hn.excl, excl_lo=hn.excl_lo, excl_hi=hn.excl_hi, out=neg, checked=True)
+    return neg
 
 
 class FullLogits(object):

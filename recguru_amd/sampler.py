@@ -55,6 +55,9 @@ def batch_seed(seed, rank, counter):
     return (seed << (RANK_BITS + COUNTER_BITS)) | (rank << COUNTER_BITS) | counter
 
 
+HARD_POOL_SEED = 0x5DEECE66D          # the hard-negative pool's draw: the batch seed with these bits flipped
+
+
 class DeviceDomain(object):
     """One domain's users on the device: CSR sequences, exclusion sets, val / test items."""
 
@@ -86,13 +89,23 @@ class DeviceDomain(object):
             prob, al = alias_table(w / w.sum())
             self.alias = (t(prob), t(al))
 
-    def batch(self, users, L_enc, L_dec, eos, n_neg, seed, shared_negs=0):
+    def batch(self, users, L_enc, L_dec, eos, n_neg, seed, shared_negs=0, hard_negs=0, hard_k=None, hard_skip=0):
+        if shared_negs > 0 and hard_negs > 0:
+            raise ValueError("hard_negs and shared_negs exclude each other: a shared list has no per-position negatives to harden")
         users = users.to(self.device).contiguous()
         seqs = hip.assemble_batch(self.items, self.offsets, users, L_enc, L_dec, eos)
         if shared_negs > 0:
             n_items = self.shared_candidates(shared_negs, seed)
         else:
             n_items = hip.sample_negatives(self.excl, self.excl_off, users, n_neg, self.V, seed, self.alias)
+        if hard_negs > 0:
+            # the private draw as always, and ONE pool for the batch under a seed of its own (the batch seed carries the rank); the
+            # users' exclusion rows are handed on as offsets into self.excl, the values are not copied
+            from .models import HardNegatives
+            k = n_neg // L_dec
+            pool = self.shared_candidates(hard_negs, seed ^ HARD_POOL_SEED)
+            n_items = HardNegatives(n_items, pool, k if not hard_k else int(hard_k), hard_skip, excl=self.excl,
+                                    excl_lo=self.excl_off[users], excl_hi=self.excl_off[users + 1])
         return seqs, n_items, self.val[users], self.test[users]
 
     def shared_candidates(self, n, seed):
@@ -110,12 +123,17 @@ class DeviceLoader(object):
     """Iterates a DeviceDomain like the reference's DataLoader over pickle_loader (train: num_n * enc_maxlen
     negatives per user; eval_n: candidate_size).  rank / world shard the users as rank::world.
     shared_negs > 0: n_items is ONE 1-D ascending list of the distinct ids among shared_negs draws, shared by the batch, instead of
-    the [B, n_neg] per-user draws (every rank draws its own: the batch seed carries the rank)."""
+    the [B, n_neg] per-user draws (every rank draws its own: the batch seed carries the rank).
+    hard_negs > 0: n_items is a models.HardNegatives -- the per-user draws plus one pool of the distinct ids among hard_negs draws,
+    from which the model's current top scorers replace the first hard_k (None: all) negatives of every position."""
 
     def __init__(self, domain, batch_size, L_enc, L_dec, eos, n_neg, seed=0, shuffle=True, rank=0, world=1, drop_last=True,
-                 shared_negs=0):
+                 shared_negs=0, hard_negs=0, hard_k=None, hard_skip=0):
         self.dom, self.bs, self.Le, self.Ld, self.eos, self.n_neg = domain, batch_size, L_enc, L_dec, eos, n_neg
         self.shared_negs = int(shared_negs)
+        self.hard = (int(hard_negs), hard_k, int(hard_skip))
+        if self.shared_negs > 0 and self.hard[0] > 0:
+            raise ValueError("hard_negs and shared_negs exclude each other: a shared list has no per-position negatives to harden")
         self.users = torch.arange(rank, domain.n, world, device=domain.device)[:max(domain.n // world, 1 if world == 1 else 0)]   # equal shards (dist.shard_users)
         self.shuffle, self.seed, self.epoch, self.drop_last = shuffle, int(seed) * 1000003 + rank, 0, drop_last
         self.seed_rank = (int(seed), int(rank))
@@ -136,7 +154,9 @@ class DeviceLoader(object):
         for i in range(self.nb):
             u = order[i * self.bs:(i + 1) * self.bs]
             seed = batch_seed(self.seed_rank[0], self.seed_rank[1], self.epoch * self.nb + i)
-            if self.shared_negs > 0:
+            if self.hard[0] > 0:
+                yield self.dom.batch(u, self.Le, self.Ld, self.eos, self.n_neg, seed, 0, *self.hard)
+            elif self.shared_negs > 0:
                 yield self.dom.batch(u, self.Le, self.Ld, self.eos, self.n_neg, seed, self.shared_negs)
             else:
                 yield self.dom.batch(u, self.Le, self.Ld, self.eos, self.n_neg, seed)

@@ -18,7 +18,7 @@ import sys
 import torch
 
 from . import ops, profiling
-from .models import check_recon_handle
+from .models import check_recon_handle, resolve_negatives
 from .optim import Adam, averaged, has_average, norm_of, options as adam_options
 
 LAMBDA = .1         # gan_training.py:21
@@ -111,6 +111,7 @@ def loss_bpr_func(model_train, enc_in, dec_in, dec_out, n_items, mask, domain, p
     """BPR loss over recommend_forward (tools/utils.py:90-127)."""
     m = _unwrap(model_train)
     h = m.recommend_forward(enc_in, dec_in, domain, mask.view(-1, param.rec_maxlen))
+    n_items = resolve_negatives(h, m.item_table(domain), dec_out, n_items, param.n_bpr_neg, mask)
     return ops.bpr_loss(h, m.item_table(domain), dec_out, n_items, mask, param.n_bpr_neg)
 
 

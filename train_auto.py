@@ -50,6 +50,11 @@ def parse():
     p.add_argument("--shared_negs", type=int, default=0,
                    help="pre-training loader only: draw this many candidates ONCE per batch and share them among all positions "
                         "(DESIGN.md 6e) instead of n_negs private negatives per position; 0 = off")
+    p.add_argument("--hard_negs", type=int, default=0,
+                   help="hard negatives (DESIGN.md 6j): draw a pool of this many candidates per batch, score it with the current model "
+                        "and train every position against the pool members it ranks highest (both loaders); 0 = off")
+    p.add_argument("--hard_k", type=int, default=0, help="--hard_negs: how many of a position's negatives are hard ones (0 = all)")
+    p.add_argument("--hard_skip", type=int, default=0, help="--hard_negs: ranks dropped from the head of the pool's order")
     p.add_argument("--pos_train", type=lambda v: v == "True", default=False,
                    help="True: learned positional table of enc_maxlen rows (the reference's pos_train) instead of the fixed sinusoid")
     p.add_argument("--weight_decay", type=float, default=0.0, help="weight decay of both optimizers (recguru_amd/optim.py); 0 = off, as the reference")
@@ -91,6 +96,8 @@ def main():
         from recguru_amd import profiling
         profiling.install(profiling.StepProfiler(args.profile, steps=args.profile_steps, skip=2, rank=0))
     L, V = param.enc_maxlen, param.vocab_size - 1
+    hard = config.hard_negs_options(param)
+    hard_of = lambda kk: config.hard_negs_options(param, kk)                # (a --hard_k above a phase's k: all of that phase's)
     item_fre = None
     if args.synthetic:
         ae = synthetic.TensorLoader(synthetic.make_domain(args.synthetic, V, L, param.n_negs, seed=1), param.batch_size, device)
@@ -100,6 +107,11 @@ def main():
         if param.shared_negs > 0:                                              # the pre-training loader draws on the device: one list per batch
             ae = sampler.DeviceLoader(sampler.DeviceDomain(seqs, val, test, V, device), param.batch_size, L, L, V + 1, L * param.n_negs,
                                       seed=1, shared_negs=param.shared_negs)
+        if hard:                                                               # every training loader draws on the device: the draws plus one scored pool per batch
+            mk_hard = lambda kk, seed, L_dec: sampler.DeviceLoader(sampler.DeviceDomain(seqs, val, test, V, device), param.batch_size, L, L_dec,
+                                                                   V + 1, L_dec * kk, seed=seed, **hard_of(kk))
+            ae = mk_hard(param.n_negs, 1, L)
+            re = re_f = mk_hard(param.num_train_neg, 2, param.rec_maxlen)
         param.candidate_size = min(param.candidate_size, V - L - 3)
         ev = sampler.DeviceEvalLoader(seqs, val, test, V, device, min(param.batch_size_val, args.synthetic), L, param.rec_maxlen,
                                       V + 1, param.candidate_size)
@@ -110,9 +122,9 @@ def main():
             item_fre = data.load_pickle(found["freq_a"][0])                 # train_auto.py:411-414
         param.vocab_size_a = param.vocab_size
         gen = lambda n, seed, **kw: data.device_loader_gen(files, param, n, "a", device, seed=seed, **kw)
-        ae = gen(param.n_negs, 1, shared_negs=param.shared_negs)            # train_auto.py:417-430
-        re = gen(param.n_bpr_neg, 2, rec=True)
-        re_f = gen(param.n_bpr_neg, 3, rec=True, wf=item_fre)
+        ae = gen(param.n_negs, 1, shared_negs=param.shared_negs, **hard_of(param.n_negs))    # train_auto.py:417-430
+        re = gen(param.n_bpr_neg, 2, rec=True, **hard_of(param.n_bpr_neg))
+        re_f = gen(param.n_bpr_neg, 3, rec=True, wf=item_fre, **hard_of(param.n_bpr_neg))
         ev = data.eval_loader_gen(files, param, "a", device, wf=item_fre)
     torch.manual_seed(1)
     at.main(param, device, ae, re, ev, re_f, item_freq=item_fre, sas_=args.sas, shared=args.share_dec, fix_enc=args.fix_enc,

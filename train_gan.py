@@ -60,6 +60,12 @@ def parse():
     p.add_argument("--shared_negs", type=int, default=0,
                    help="reconstruction loaders only: draw this many candidates ONCE per batch and share them among all positions "
                         "(sampled softmax over one candidate list, DESIGN.md 6e) instead of n_negs private negatives per position; 0 = off")
+    p.add_argument("--hard_negs", type=int, default=0,
+                   help="hard negatives (DESIGN.md 6j): draw a pool of this many candidates per batch, score it with the current model "
+                        "and train every position against the pool members it ranks highest (reconstruction and recommender "
+                        "loaders); 0 = off")
+    p.add_argument("--hard_k", type=int, default=0, help="--hard_negs: how many of a position's negatives are hard ones (0 = all)")
+    p.add_argument("--hard_skip", type=int, default=0, help="--hard_negs: ranks dropped from the head of the pool's order")
     p.add_argument("--pos_train", type=str2bool_par, default=False,
                    help="True: learned positional tables of enc_maxlen rows for both domains instead of the fixed sinusoid "
                         "(this project's extension of the cross model)")
@@ -106,6 +112,8 @@ def main():
         profiling.install(profiling.StepProfiler(args.profile, steps=args.profile_steps, skip=2, rank=rank))
 
     L, k = param.enc_maxlen, param.n_negs
+    hard = param_c.hard_negs_options(param)
+    hard_of = lambda kk: param_c.hard_negs_options(param, kk)          # (a --hard_k above a phase's k: all of that phase's)
     if args.synthetic:
         dom_a = synthetic.make_domain(args.synthetic, param.vocab_size_a - 1, L, k, seed=1)
         dom_b = synthetic.make_domain(args.synthetic, param.vocab_size_b - 1, L, k, seed=2)
@@ -122,6 +130,16 @@ def main():
         rec_dom = synthetic.make_domain(args.synthetic, (param.vocab_size_a if args.target_domain == "a"
                                                          else param.vocab_size_b) - 1, L, param.n_bpr_neg, seed=3)
         rec_loaders = [mk(rec_dom), mk(rec_dom)]
+        if hard:                                                   # every training loader draws on the device: the draws plus one scored pool per batch
+            from recguru_amd import sampler
+
+            def mk_hard(V, seed, L_dec, kk):
+                seqs, val, test, _ = synthetic.make_users(args.synthetic, V, L, seed=seed)
+                return sampler.DeviceLoader(sampler.DeviceDomain(seqs, val, test, V, device), param.batch_size, L, L_dec, V + 1, L_dec * kk,
+                                            seed=10 + seed, rank=rank, world=world, **hard_of(kk))
+            Vr = (param.vocab_size_a if args.target_domain == "a" else param.vocab_size_b) - 1
+            ae_loaders = [mk_hard(param.vocab_size_a - 1, 1, L, k), mk_hard(param.vocab_size_b - 1, 2, L, k)]
+            rec_loaders = [mk_hard(Vr, 3, param.rec_maxlen, param.n_bpr_neg), mk_hard(Vr, 3, param.rec_maxlen, param.n_bpr_neg)]
         # ranking evaluation at the reference's evaluation points (gan_training.py:569-580)
         from recguru_amd import sampler
         Vt = (param.vocab_size_a if args.target_domain == "a" else param.vocab_size_b) - 1
@@ -142,10 +160,11 @@ def main():
                 sys.exit("train_gan.py: no '%s' pickle under %s (train_gan.py:65-79 naming)" % (need, param.data_path))
         # shuffled loaders with FRESH negatives per batch (data_loader.py:276-316,455-483), on the device
         gen = lambda f, n, dom, seed, **kw: Dataloader.device_loader_gen(f, param, n, dom, device, rank, world, seed=seed, **kw)
-        ae_loaders = [gen(files["a"], k, "a", 11, shared_negs=param.shared_negs), gen(files["b"], k, "b", 12, shared_negs=param.shared_negs)]
+        ae_loaders = [gen(files["a"], k, "a", 11, shared_negs=param.shared_negs, **hard_of(k)),
+                      gen(files["b"], k, "b", 12, shared_negs=param.shared_negs, **hard_of(k))]
         freq = Dataloader.load_pickle(files["freq_" + t][0])
-        rec_loaders = [gen(files[t], param.n_bpr_neg, t, 13, rec=True),
-                       gen(files[t], param.n_bpr_neg, t, 14, rec=True, wf=freq)]
+        rec_loaders = [gen(files[t], param.n_bpr_neg, t, 13, rec=True, **hard_of(param.n_bpr_neg)),
+                       gen(files[t], param.n_bpr_neg, t, 14, rec=True, wf=freq, **hard_of(param.n_bpr_neg))]
         # train_loader_re_test_{a,b} (train_gan.py:91-92,100-101): evaluated every 30 iterations past 0.8 * iterations
         test_loaders = Dataloader.eval_loader_gen(files[t], param, t, device, 0, 1, wf=freq)        # unsharded, see above
     torch.manual_seed(1)                                           # gan_training.py:20 (same initial weights on every rank)
