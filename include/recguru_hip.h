@@ -482,6 +482,8 @@ typedef struct {
   const float* gout;          /* [1] upstream gradient (backward only) */
   void* dh; float* dE;        /* backward outputs */
   long long ntok; int d; int k; int mode; long long skip_row;
+  const float* neg_bias;      /* [rows] f32 or NULL: added to the logit of negative row j by its item id (logQ correction) */
+  const float* pos_bias;      /* [ntok] f32 or NULL: added to the positive's logit */
 } rg_item_loss_args;
 int rg_item_loss_fwd(const rg_item_loss_args* args /* host */, int dtype, void* stream);
 int rg_item_loss_bwd(const rg_item_loss_args* args /* host */, int dtype, void* stream);

@@ -48,6 +48,7 @@ class get_param(object):
         self.hard_negs = int(_opt(args, "hard_negs", 0))           # > 0: hard negatives, the size of the pool drawn per batch; 0 = off
         self.hard_k = int(_opt(args, "hard_k", 0))                 # how many of a position's negatives are hard ones; 0 = all of them
         self.hard_skip = int(_opt(args, "hard_skip", 0))           # ranks dropped from the head of the pool's order
+        self.logq = bool(_opt(args, "logq", False))                # True: logQ correction of the sampled reconstruction loss
         self.pos_train = bool(_opt(args, "pos_train", False))      # True: learned positional table (blocks.PositionalEncodingM) instead of the sinusoid
         # optimizer options (recguru_amd/optim.py), all neutral by default: the reference configures none of them
         self.weight_decay = float(_opt(args, "weight_decay", 0.0))
@@ -134,6 +135,18 @@ class get_param(object):
         self.smoothing = 0.1
         self.dis_dim = self.d_model * 5
         self.training_steps_tune = int(_opt(args, "steps_tune", 300))   # ":237  # for testing"
+
+
+def logq_options(param):
+    """The reconstruction loaders' logQ argument of a run (--logq): {} when the feature is off, else the keyword of
+    sampler.DeviceLoader / data.device_loader_gen.  ValueError where the run has no draws to correct."""
+    if not getattr(param, "logq", False):
+        return {}
+    if not param.decoder_neg:
+        raise ValueError("--logq needs sampled negatives (decoder_neg=True): the full-catalogue loss has nothing to correct")
+    if param.hard_negs > 0:
+        raise ValueError("--logq and --hard_negs exclude each other: hard columns are not draws from the sampler's distribution")
+    return {"logq": True}
 
 
 def hard_negs_options(param, k=None):

@@ -12,6 +12,7 @@
 // Backward recomputes the dots (rows come from L2 / Infinity Cache), forms
 // c_j = dl_t/dlogit_j * mask_t * gout / sum(mask), accumulates dh_t = sum_j c_j E[j] in registers and
 // scatters c_j * h_t into the dense f32 table gradient with full-row (256 B per instruction) atomics.
+#include <stdio.h>
 #include <stdlib.h>
 #include "rg_common.hip.h"
 #include "rg_det.hip.h"
@@ -150,6 +151,14 @@ __global__ __launch_bounds__(64 * LW) void item_loss_bwd_kernel(rg_item_loss_arg
 // ------------------------------------------------------------------------------------------------
 #define RG_U 4
 
+// logQ correction (the BIAS instantiations; sampled softmax only): what is added to the logit of row idx of position t --
+// pos_bias[t] for the positive (idx 0), neg_bias[item] for negative idx in 1..k; a NULL table and the padding rows idx >= n give 0
+// (a padding row re-reads the positive's ROW, never a bias).  Called for live positions only.
+__device__ __forceinline__ float row_bias(const rg_item_loss_args& a, long long t, int idx, int n, long long item) {
+  if (idx == 0) return a.pos_bias ? a.pos_bias[t] : 0.f;
+  return (a.neg_bias && idx < n) ? a.neg_bias[item] : 0.f;
+}
+
 template <int LPR>
 __device__ __forceinline__ float group_sum(float v) {
 #pragma unroll
@@ -157,7 +166,7 @@ __device__ __forceinline__ float group_sum(float v) {
   return v;
 }
 
-template <typename T, int LPR>
+template <typename T, int LPR, bool BIAS>
 __global__ __launch_bounds__(64 * LW) void item_loss_fwd_rows_kernel(rg_item_loss_args a) {
   constexpr int G = 64 / LPR;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -183,6 +192,11 @@ __global__ __launch_bounds__(64 * LW) void item_loss_fwd_rows_kernel(rg_item_los
       }
 #pragma unroll
       for (int u = 0; u < RG_U; ++u) load8(e[u], E + (size_t)item[u] * d + 8 * li);
+      float bs[RG_U];                                      // (BIAS) requested with the rows, from the same ids
+      if (BIAS) {
+#pragma unroll
+        for (int u = 0; u < RG_U; ++u) bs[u] = row_bias(a, t, i0 + u * G + gi, n, item[u]);
+      }
 #pragma unroll
       for (int u = 0; u < RG_U; ++u) {
         const int idx = i0 + u * G + gi;
@@ -190,6 +204,7 @@ __global__ __launch_bounds__(64 * LW) void item_loss_fwd_rows_kernel(rg_item_los
 #pragma unroll
         for (int j = 0; j < 8; ++j) dot += e[u][j] * h[j];
         dot = group_sum<LPR>(dot);
+        if (BIAS) dot += bs[u];
         if (idx < n) {
           if (idx == 0) l0 = dot;
           if (a.mode == RG_LOSS_SAMPLED_CE) {
@@ -232,7 +247,7 @@ __global__ __launch_bounds__(64 * LW) void item_loss_fwd_rows_kernel(rg_item_los
   }
 }
 
-template <typename T, int LPR, bool CBUF>
+template <typename T, int LPR, bool CBUF, bool BIAS>
 __global__ __launch_bounds__(64 * LW) void item_loss_bwd_rows_kernel(rg_item_loss_args a, float* __restrict__ cbuf) {
   constexpr int G = 64 / LPR;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -268,6 +283,11 @@ __global__ __launch_bounds__(64 * LW) void item_loss_bwd_rows_kernel(rg_item_los
         }
 #pragma unroll
         for (int u = 0; u < RG_U; ++u) load8(e[u], E + (size_t)item[u] * d + 8 * li);
+        float bs[RG_U];
+        if (BIAS) {
+#pragma unroll
+          for (int u = 0; u < RG_U; ++u) bs[u] = row_bias(a, t, i0 + u * G + gi, n, item[u]);
+        }
 #pragma unroll
         for (int u = 0; u < RG_U; ++u) {
           const int idx = i0 + u * G + gi;
@@ -275,6 +295,7 @@ __global__ __launch_bounds__(64 * LW) void item_loss_bwd_rows_kernel(rg_item_los
 #pragma unroll
           for (int j = 0; j < 8; ++j) dot += e[u][j] * h[j];
           dot = group_sum<LPR>(dot);
+          if (BIAS) dot += bs[u];
           float c;
           if (idx == 0) l0 = dot;
           if (a.mode == RG_LOSS_SAMPLED_CE) c = (__expf(dot - aux) - (idx == 0 ? 1.f : 0.f)) * w;
@@ -306,7 +327,7 @@ __global__ __launch_bounds__(64 * LW) void item_loss_bwd_rows_kernel(rg_item_los
 // c and dh are produced for gout = 1 (w = mask_t / sums[1], sums[1] = the mask count, which the caller supplies
 // BEFORE the launch) and the backward scales them (bin_fill multiplies c by gout, rg_scale_dev does dh; both
 // are exact no-ops for gout == 1, the value a plain loss.backward() sends).  NIT batches of G * RG_U rows.
-template <typename T, int LPR, int NIT>
+template <typename T, int LPR, int NIT, bool BIAS>
 __global__ __launch_bounds__(64 * LW) void item_loss_train_rows_kernel(rg_item_loss_args a, float* __restrict__ cbuf) {
   constexpr int G = 64 / LPR;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -339,6 +360,13 @@ __global__ __launch_bounds__(64 * LW) void item_loss_train_rows_kernel(rg_item_l
       for (int it = 0; it < NIT; ++it)
 #pragma unroll
         for (int u = 0; u < RG_U; ++u) load8(e[it][u], E + (size_t)item[it][u] * d + 8 * li);
+      float bs[NIT][RG_U];
+      if (BIAS) {
+#pragma unroll
+        for (int it = 0; it < NIT; ++it)
+#pragma unroll
+          for (int u = 0; u < RG_U; ++u) bs[it][u] = row_bias(a, t, (it * RG_U + u) * G + gi, n, item[it][u]);
+      }
       float mx = -INFINITY, sm = 0.f, ns = 0.f, l0 = 0.f;      // per row group
 #pragma unroll
       for (int it = 0; it < NIT; ++it)
@@ -349,6 +377,7 @@ __global__ __launch_bounds__(64 * LW) void item_loss_train_rows_kernel(rg_item_l
 #pragma unroll
           for (int j = 0; j < 8; ++j) s += e[it][u][j] * h[j];
           s = group_sum<LPR>(s);
+          if (BIAS) s += bs[it][u];
           dot[it][u] = s;
           if (idx < n) {
             if (idx == 0) l0 = s;
@@ -422,7 +451,7 @@ __global__ __launch_bounds__(64 * LW) void item_loss_train_rows_kernel(rg_item_l
 // of rows --, and the rows of batch s + 1 are requested BEFORE batch s is reduced (two register buffers), so a wave keeps 2 x RG_U x G rows
 // in flight instead of RG_U x G.  (The plain form -- ids loaded per batch, one buffer -- gave bit-identical logits, lse, loss and dh; was
 // measured, removed: DESIGN.md 6a.)
-template <typename T, int LPR>
+template <typename T, int LPR, bool BIAS>
 __global__ __launch_bounds__(64 * LW) void item_loss_train_online2_kernel(rg_item_loss_args a, float* __restrict__ cbuf) {
   constexpr int G = 64 / LPR, RS = G * RG_U, NS = 64 / RS;          // rows per step, steps per block of 64 rows (even)
   static_assert(NS % 2 == 0, "two register buffers alternate inside a block of 64 rows");
@@ -450,6 +479,8 @@ __global__ __launch_bounds__(64 * LW) void item_loss_train_online2_kernel(rg_ite
         const long long v = negt[min(max(idx - 1, 0), k - 1)];       // unconditional load from a clamped address
         return (idx == 0 || idx >= n) ? pos : v;
       };
+      // (BIAS) lane l: the bias of row i0 + l, by the id load_ids(i0) gave this lane
+      auto load_bias = [&](int i0, long long id) -> float { return row_bias(a, t, i0 + lane, n, id); };
       Frag<T> e[2][RG_U];                                 // RAW rows (bf16: 4 registers each) until they are reduced
       auto issue = [&](Frag<T> (&eb)[RG_U], long long ids, int j0) {
         const int idlo = (int)(ids & 0xFFFFFFFFll), idhi = (int)(ids >> 32);
@@ -464,10 +495,17 @@ __global__ __launch_bounds__(64 * LW) void item_loss_train_online2_kernel(rg_ite
       for (int j = 0; j < 8; ++j) { A[j] = 0.f; e0[j] = 0.f; }
       float mx = -INFINITY, sm = 0.f, l0 = 0.f;          // per row group
       long long idn = load_ids(0);
+      // (BIAS) a bias is addressed by its row's id: lane l asks for the bias of row l of the NEXT block in the block's last step,
+      // right behind that block's first rows -- its ids, requested a block earlier, have arrived by then (the row requests need
+      // them), and the bias is back with those rows: no dependent latency in front of any row batch, and one register (bc) held
+      // through the block.  The biases reach the row groups as the ids do (ds_bpermute).
+      float bc = 0.f, bn = 0.f;
+      if (BIAS) bn = load_bias(0, idn);
       issue(e[0], idn, 0);
       for (int i0 = 0; i0 < n; i0 += 64) {
         const long long idc = idn;
         idn = load_ids(min(i0 + 64, n - 1));             // (unconditional; unused past the last block)
+        if (BIAS) bc = bn;
 #pragma unroll 1
         for (int sp = 0; sp < NS; sp += 2) {               // two steps per trip: the register buffers keep compile-time indices
 #pragma unroll
@@ -477,6 +515,7 @@ __global__ __launch_bounds__(64 * LW) void item_loss_train_online2_kernel(rg_ite
             // reduced; ONE unconditional load sequence from selected ids (a load under a branch is waited for at its join)
             const bool wrap = s + 1 >= NS;
             issue(e[(half + 1) & 1], wrap ? idn : idc, wrap ? 0 : (s + 1) * RS);
+            if (BIAS && half == 1) { if (wrap) bn = load_bias(min(i0 + 64, n - 1), idn); }
             Frag<T> (&eb)[RG_U] = e[half];
 #pragma unroll
             for (int u = 0; u < RG_U; ++u) {
@@ -488,6 +527,7 @@ __global__ __launch_bounds__(64 * LW) void item_loss_train_online2_kernel(rg_ite
 #pragma unroll
               for (int j = 0; j < 8; ++j) dot += ev[j] * h[j];
               dot = group_sum<LPR>(dot);
+              if (BIAS) dot += __shfl(bc, s * RS + u * G + gi);
               if (idx < n) {
                 if (idx == 0) {
                   l0 = dot;
@@ -542,23 +582,47 @@ __global__ __launch_bounds__(64 * LW) void item_loss_train_online2_kernel(rg_ite
 }
 
 
+// logQ biases: either pointer selects the BIAS instantiations; refused before any launch where no kernel takes them
+static bool has_bias(const rg_item_loss_args& a) { return a.neg_bias || a.pos_bias; }
+static int check_bias(const rg_item_loss_args& a, const char* who) {
+  if (!has_bias(a)) return 0;
+  char msg[160];
+  if (a.mode != RG_LOSS_SAMPLED_CE) {
+    snprintf(msg, sizeof msg, "%s: neg_bias / pos_bias (logQ correction) go with the sampled softmax only, not with a BPR mode", who);
+    return rg_set_error_msg(RG_ERR_UNSUPPORTED, msg);
+  }
+  if (!(a.d == 64 || a.d == 128 || a.d == 256)) {
+    snprintf(msg, sizeof msg, "%s: neg_bias / pos_bias need d in {64,128,256}", who);
+    return rg_set_error_msg(RG_ERR_UNSUPPORTED, msg);
+  }
+  if (a.neg_bias && !a.table) {
+    snprintf(msg, sizeof msg, "%s: neg_bias given with table NULL", who);
+    return rg_set_error_msg(RG_ERR_INVALID, msg);
+  }
+  return 0;
+}
+
 template <typename T>
 static int launch(const rg_item_loss_args& a, bool bwd, hipStream_t s) {
   long long g = (a.ntok + LW - 1) / LW;
   if (g > 256 * 32) g = 256 * 32;
   dim3 grid((int)g), block(64 * LW);
-#define RG_R(LPR)                                                                             \
+  const bool bias = has_bias(a);
+  if (int rc = check_bias(a, "item_loss")) return rc;
+#define RG_R1(LPR, BIAS)                                                                      \
   do {                                                                                        \
-    if (bwd) hipLaunchKernelGGL((item_loss_bwd_rows_kernel<T, LPR, false>), grid, block, 0, s, a, (float*)nullptr);   \
-    else hipLaunchKernelGGL((item_loss_fwd_rows_kernel<T, LPR>), grid, block, 0, s, a);       \
+    if (bwd) hipLaunchKernelGGL((item_loss_bwd_rows_kernel<T, LPR, false, BIAS>), grid, block, 0, s, a, (float*)nullptr);   \
+    else hipLaunchKernelGGL((item_loss_fwd_rows_kernel<T, LPR, BIAS>), grid, block, 0, s, a); \
     RG_CHECK_LAUNCH();                                                                        \
     return 0;                                                                                 \
   } while (0)
+#define RG_R(LPR) do { if (bias) RG_R1(LPR, true); else RG_R1(LPR, false); } while (0)
   if (a.d == 64) RG_R(8);
   if (a.d == 128) RG_R(16);
   if (a.d == 256) RG_R(32);
 #undef RG_R
-#define RG_L(NPL)                                                                   \
+#undef RG_R1
+#define RG_L(NPL)                                                                  \
   if (bwd) hipLaunchKernelGGL((item_loss_bwd_kernel<T, NPL>), grid, block, 0, s, a); \
   else hipLaunchKernelGGL((item_loss_fwd_kernel<T, NPL>), grid, block, 0, s, a)
   if (a.d <= 64) { RG_L(1); }
@@ -1062,6 +1126,8 @@ static int launch_binned(const rg_item_loss_args& a, const float* coef, void* ws
                          const DropCfg* drop = nullptr) {
   const int n = a.k + 1;
   const long long npairs = a.ntok * n;
+  const bool bias = !coef && has_bias(a);        // (the scatter half works from coefficients: the biases are in them already)
+  if (bias) { if (int rc = check_bias(a, "item_loss_bwd_binned")) return rc; }
   const size_t need = rg_item_loss_bwd_binned_workspace(a.ntok, a.k, a.d, table_rows);
   if (!need) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "item_loss_bwd_binned: needs d in {64,128,256}, <= 8192 bins of 64 (or 256) rows, < 2^31 pairs, < 2^26 (2^24) positions");
   if (!ws || ws_bytes < need) return rg_set_error_msg(RG_ERR_INVALID, "item_loss_bwd_binned: workspace too small");
@@ -1090,9 +1156,14 @@ static int launch_binned(const rg_item_loss_args& a, const float* coef, void* ws
   long long g = (a.ntok + LW - 1) / LW;
   if (g > 256 * 32) g = 256 * 32;
   if (coef) {}
-  else if (a.d == 64) hipLaunchKernelGGL((item_loss_bwd_rows_kernel<T, 8, true>), dim3((int)g), dim3(64 * LW), 0, s, a, w.c);
-  else if (a.d == 128) hipLaunchKernelGGL((item_loss_bwd_rows_kernel<T, 16, true>), dim3((int)g), dim3(64 * LW), 0, s, a, w.c);
-  else hipLaunchKernelGGL((item_loss_bwd_rows_kernel<T, 32, true>), dim3((int)g), dim3(64 * LW), 0, s, a, w.c);
+  else if (bias) {
+    if (a.d == 64) hipLaunchKernelGGL((item_loss_bwd_rows_kernel<T, 8, true, true>), dim3((int)g), dim3(64 * LW), 0, s, a, w.c);
+    else if (a.d == 128) hipLaunchKernelGGL((item_loss_bwd_rows_kernel<T, 16, true, true>), dim3((int)g), dim3(64 * LW), 0, s, a, w.c);
+    else hipLaunchKernelGGL((item_loss_bwd_rows_kernel<T, 32, true, true>), dim3((int)g), dim3(64 * LW), 0, s, a, w.c);
+  }
+  else if (a.d == 64) hipLaunchKernelGGL((item_loss_bwd_rows_kernel<T, 8, true, false>), dim3((int)g), dim3(64 * LW), 0, s, a, w.c);
+  else if (a.d == 128) hipLaunchKernelGGL((item_loss_bwd_rows_kernel<T, 16, true, false>), dim3((int)g), dim3(64 * LW), 0, s, a, w.c);
+  else hipLaunchKernelGGL((item_loss_bwd_rows_kernel<T, 32, true, false>), dim3((int)g), dim3(64 * LW), 0, s, a, w.c);
   // K2..K4
   w.ppw = w.nbins > 4096 ? RG_PPW_WIDE : RG_PPW;
   const int gp = (int)((npairs + w.ppw - 1) / w.ppw);
@@ -1161,28 +1232,38 @@ static int launch_train(const rg_item_loss_args& a, float* coef, hipStream_t s) 
   const int nit = train_nit(a.k, a.d);
   if (!(a.d == 64 || a.d == 128 || a.d == 256)) return rg_set_error_msg(RG_ERR_UNSUPPORTED, "item_loss_train: needs d in {64,128,256}");
   if (!coef || !a.dh || !a.sums) return rg_set_error_msg(RG_ERR_INVALID, "item_loss_train: coef, dh and sums are required");
+  const bool bias = has_bias(a);
+  if (int rc = check_bias(a, "item_loss_train")) return rc;
   long long g = (a.ntok + LW - 1) / LW;
   if (g > 256 * 32) g = 256 * 32;
   dim3 grid((int)g), block(64 * LW);
   if (!nit) {       // more rows than four register batches: the online form
     if (a.mode != RG_LOSS_SAMPLED_CE || !a.aux_tok)
       return rg_set_error_msg(RG_ERR_UNSUPPORTED, "item_loss_train: 1+k beyond 4 row batches takes the online form: sampled softmax only, aux_tok [ntok] required");
-    if (a.d == 64) hipLaunchKernelGGL((item_loss_train_online2_kernel<T, 8>), grid, block, 0, s, a, coef);
-    else if (a.d == 128) hipLaunchKernelGGL((item_loss_train_online2_kernel<T, 16>), grid, block, 0, s, a, coef);
-    else hipLaunchKernelGGL((item_loss_train_online2_kernel<T, 32>), grid, block, 0, s, a, coef);
+#define RG_ON(BIAS)                                                                                                       \
+  do {                                                                                                                    \
+    if (a.d == 64) hipLaunchKernelGGL((item_loss_train_online2_kernel<T, 8, BIAS>), grid, block, 0, s, a, coef);          \
+    else if (a.d == 128) hipLaunchKernelGGL((item_loss_train_online2_kernel<T, 16, BIAS>), grid, block, 0, s, a, coef);   \
+    else hipLaunchKernelGGL((item_loss_train_online2_kernel<T, 32, BIAS>), grid, block, 0, s, a, coef);                   \
+  } while (0)
+    if (bias) RG_ON(true);
+    else RG_ON(false);
+#undef RG_ON
     RG_CHECK_LAUNCH();
     return 0;
   }
-#define RG_TR(LPR)                                                                                           \
-  do {                                                                                                       \
-    if (nit == 1) hipLaunchKernelGGL((item_loss_train_rows_kernel<T, LPR, 1>), grid, block, 0, s, a, coef);  \
-    else if (nit == 2) hipLaunchKernelGGL((item_loss_train_rows_kernel<T, LPR, 2>), grid, block, 0, s, a, coef); \
-    else hipLaunchKernelGGL((item_loss_train_rows_kernel<T, LPR, 4>), grid, block, 0, s, a, coef);           \
+#define RG_TR1(LPR, BIAS)                                                                                          \
+  do {                                                                                                             \
+    if (nit == 1) hipLaunchKernelGGL((item_loss_train_rows_kernel<T, LPR, 1, BIAS>), grid, block, 0, s, a, coef);  \
+    else if (nit == 2) hipLaunchKernelGGL((item_loss_train_rows_kernel<T, LPR, 2, BIAS>), grid, block, 0, s, a, coef); \
+    else hipLaunchKernelGGL((item_loss_train_rows_kernel<T, LPR, 4, BIAS>), grid, block, 0, s, a, coef);           \
   } while (0)
+#define RG_TR(LPR) do { if (bias) RG_TR1(LPR, true); else RG_TR1(LPR, false); } while (0)
   if (a.d == 64) RG_TR(8);
   else if (a.d == 128) RG_TR(16);
   else RG_TR(32);
 #undef RG_TR
+#undef RG_TR1
   RG_CHECK_LAUNCH();
   return 0;
 }

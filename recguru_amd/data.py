@@ -58,11 +58,12 @@ def domain_from_pickles(files, L, eos, V, k, seed=0, wf=None):
 
 
 def device_loader_gen(files, param, num_n, domain="a", device="cuda", rank=0, world=1, seed=0, wf=None, batch_size=None,
-                      eval_n=False, rec=False, exclude_val=False, shared_negs=0, hard_negs=0, hard_k=None, hard_skip=0):
+                      eval_n=False, rec=False, exclude_val=False, shared_negs=0, hard_negs=0, hard_k=None, hard_skip=0, logq=False):
     """dataloader_gen on the device: the pickles' users go to the GPU as CSR rows once; every batch
     is assembled (seq_padding) and gets FRESH negatives (enc_maxlen * num_n per user, or candidate_size with eval_n)
     by two kernel launches -- recguru_amd.sampler.  shared_negs > 0: one candidate list per batch instead (DeviceLoader);
-    hard_negs > 0: the draws plus one scored pool per batch (models.HardNegatives)."""
+    hard_negs > 0: the draws plus one scored pool per batch (models.HardNegatives); logq=True: the draws (or the shared list) with
+    their logQ correction (models.LogQNegatives)."""
     from .sampler import DeviceDomain, DeviceLoader
     eos = param.vocab_size_a if domain == "a" else param.vocab_size_b
     seqs, val, test = [], [], []
@@ -75,7 +76,7 @@ def device_loader_gen(files, param, num_n, domain="a", device="cuda", rank=0, wo
     n_neg = param.candidate_size if eval_n else param.enc_maxlen * num_n
     return DeviceLoader(dom, batch_size or param.batch_size, param.enc_maxlen, param.rec_maxlen if rec else param.enc_maxlen,
                         eos, n_neg, seed=seed, shuffle=True, rank=rank, world=world, shared_negs=shared_negs,
-                        hard_negs=hard_negs, hard_k=hard_k, hard_skip=hard_skip)
+                        hard_negs=hard_negs, hard_k=hard_k, hard_skip=hard_skip, logq=logq)
 
 
 def users_from_pickles(files):

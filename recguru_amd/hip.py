@@ -128,7 +128,7 @@ class LnBwdArgs(ctypes.Structure):
 class ItemLossArgs(ctypes.Structure):
     _fields_ = [("h", c_p), ("table", c_p), ("pos", c_p), ("neg", c_p), ("mask", c_p), ("aux_tok", c_p),
                 ("sums", c_p), ("gout", c_p), ("dh", c_p), ("dE", c_p), ("ntok", c_ll), ("d", c_i), ("k", c_i),
-                ("mode", c_i), ("skip_row", c_ll)]
+                ("mode", c_i), ("skip_row", c_ll), ("neg_bias", c_p), ("pos_bias", c_p)]
 
 
 def _check_screened(path):
@@ -997,15 +997,30 @@ def cast(src, dtype, transpose=False):
     return dst if (mode or src.dim() > 1) else dst.reshape(src.shape)
 
 
-def item_loss_fwd(h, table, pos, neg, mask, k, mode):
+def _item_bias(neg_bias, pos_bias, table, ntok):
+    """The two trailing fields of ItemLossArgs: the logQ biases, checked.  neg_bias: one f32 per table row, gathered by
+    item id for the negatives of a live position; pos_bias: one f32 per position, added to the positive's logit.  None = off."""
+    for name, b, n in (("neg_bias", neg_bias, table.shape[0]), ("pos_bias", pos_bias, ntok)):
+        if b is None:
+            continue
+        if b.dtype != torch.float32 or not b.is_contiguous() or b.device != table.device:
+            raise ValueError("item loss: %s must be a contiguous f32 tensor on the table's device" % name)
+        if b.numel() != n:
+            raise ValueError("item loss: %s has %d elements, expected %d (%s)"
+                             % (name, b.numel(), n, "one per table row" if name == "neg_bias" else "one per position"))
+    return _p(neg_bias), _p(pos_bias)
+
+
+def item_loss_fwd(h, table, pos, neg, mask, k, mode, neg_bias=None, pos_bias=None):
     ntok, d = h.shape
     assert h.is_contiguous() and table.is_contiguous() and table.dtype == h.dtype
     assert pos.dtype == torch.int64 and neg.dtype == torch.int64 and pos.numel() == ntok and neg.numel() == ntok * k
+    nb, pb = _item_bias(neg_bias, pos_bias, table, ntok)
     aux = torch.empty(ntok, device=h.device, dtype=torch.float32)
     sums = torch.zeros(2, device=h.device, dtype=torch.float32)
     sc = _DetScope() if DETERMINISTIC else None
     a = ItemLossArgs(_p(h), _p(table), _p(pos), _p(neg), _p(mask), _p(aux), _p(sc.take(sums, "s") if sc else sums), None, None, None,
-                     ntok, d, k, mode, -1)
+                     ntok, d, k, mode, -1, nb, pb)
     try:
         _check(lib().rg_item_loss_fwd(ctypes.byref(a), dt_of(h), _stream()), "rg_item_loss_fwd")
     finally:
@@ -1259,7 +1274,7 @@ def item_loss_bwd_binned_supported(ntok, k, d, table_rows):
     return int(fn(c_ll(ntok), k, d, c_ll(table_rows)))
 
 
-def item_loss_bwd_binned(h, table, pos, neg, mask, k, mode, aux, sums, gout, dE, skip_row=-1):
+def item_loss_bwd_binned(h, table, pos, neg, mask, k, mode, aux, sums, gout, dE, skip_row=-1, neg_bias=None, pos_bias=None):
     """item_loss_bwd with the table gradient built by counting sort + LDS accumulation (loss.hip); the scratch
     buffer is cached per device and grows on demand."""
     ntok, d = h.shape
@@ -1271,8 +1286,9 @@ def item_loss_bwd_binned(h, table, pos, neg, mask, k, mode, aux, sums, gout, dE,
         ws = torch.empty(need, device=h.device, dtype=torch.uint8)
         _BIN_WS[h.device] = ws
     dh = torch.empty_like(h)
+    nb, pb = _item_bias(neg_bias, pos_bias, table, ntok)
     a = ItemLossArgs(_p(h), _p(table), _p(pos), _p(neg), _p(mask), _p(aux), _p(sums), _p(gout), _p(dh), _p(dE), ntok,
-                     d, k, mode, skip_row)
+                     d, k, mode, skip_row, nb, pb)
     _check(lib().rg_item_loss_bwd_binned(ctypes.byref(a), c_ll(table.shape[0]), _vp(ws), ctypes.c_size_t(need),
                                          dt_of(h), _stream()), "rg_item_loss_bwd_binned")
     return dh
@@ -1284,7 +1300,7 @@ def item_loss_train_supported(k, d):
 
 
 @_det_accum(sums="S")
-def item_loss_train(h, table, pos, neg, mask, k, mode, sums, lse=None):
+def item_loss_train(h, table, pos, neg, mask, k, mode, sums, lse=None, neg_bias=None, pos_bias=None):
     """Loss sum into sums[0] (sums[1] = the mask count, set by the caller) plus, for an upstream gradient of 1,
     the coefficients [ntok*(1+k)] f32 and dh [ntok,d]: one gather of the rows instead of two.
     lse [ntok] f32 (the online form, item_loss_train_supported() == 2): receives the log-sum-exp; coef then holds the RAW
@@ -1294,8 +1310,9 @@ def item_loss_train(h, table, pos, neg, mask, k, mode, sums, lse=None):
     assert pos.dtype == torch.int64 and neg.dtype == torch.int64 and pos.numel() == ntok and neg.numel() == ntok * k
     coef = torch.empty(ntok * (k + 1), device=h.device, dtype=torch.float32)
     dh = torch.empty_like(h)
+    nb, pb = _item_bias(neg_bias, pos_bias, table, ntok)
     a = ItemLossArgs(_p(h), _p(table), _p(pos), _p(neg), _p(mask), _p(lse), _p(sums), None, _p(dh), None, ntok, d, k,
-                     mode, -1)
+                     mode, -1, nb, pb)
     _check(lib().rg_item_loss_train(ctypes.byref(a), _vp(coef), dt_of(h), _stream()), "rg_item_loss_train")
     return coef, dh
 
@@ -1471,11 +1488,12 @@ def scale_dev(x, s):
 
 
 @_det_accum(dE="g")
-def item_loss_bwd(h, table, pos, neg, mask, k, mode, aux, sums, gout, dE, skip_row=-1):
+def item_loss_bwd(h, table, pos, neg, mask, k, mode, aux, sums, gout, dE, skip_row=-1, neg_bias=None, pos_bias=None):
     ntok, d = h.shape
     dh = torch.empty_like(h)
+    nb, pb = _item_bias(neg_bias, pos_bias, table, ntok)
     a = ItemLossArgs(_p(h), _p(table), _p(pos), _p(neg), _p(mask), _p(aux), _p(sums), _p(gout), _p(dh), _p(dE), ntok,
-                     d, k, mode, skip_row)
+                     d, k, mode, skip_row, nb, pb)
     _check(lib().rg_item_loss_bwd(ctypes.byref(a), dt_of(h), _stream()), "rg_item_loss_bwd")
     return dh
 

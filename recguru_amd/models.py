@@ -28,10 +28,15 @@ def _f32_mask(ids, pad):
 class SampledLogits(object):
     """Deferred logits of the positive + k sampled negatives per position
     (AutoEnc4Rec_cross.py:201-215).  Holds the decoder states and the item ids.  neg may be a HardNegatives: it becomes the [n, k] ids
-    when a loss is asked for, under that loss's mask (resolve_negatives: the positions the loss counts are the ones that are scored)."""
+    when a loss is asked for, under that loss's mask (resolve_negatives: the positions the loss counts are the ones that are scored).
+    neg_bias [table rows] / pos_bias [one per position]: the logQ correction (LogQNegatives), added to the negatives'
+    logits by item id and to the positive's logit in the sampled softmax."""
 
-    def __init__(self, h, table, pos, neg, k, skip_row=-1):
+    def __init__(self, h, table, pos, neg, k, skip_row=-1, neg_bias=None, pos_bias=None):
         self.h, self.table, self.pos, self.neg, self.k, self.skip_row = h, table, pos, neg, k, skip_row
+        if pos_bias is not None and pos_bias.numel() != pos.numel():
+            raise ValueError("pos_bias holds %d values for %d positions" % (pos_bias.numel(), pos.numel()))
+        self.neg_bias, self.pos_bias = neg_bias, pos_bias
 
     def negatives(self, mask=None):
         """The [n, k] negative ids the losses see (mask None: every position counts, what dense() shows)."""
@@ -41,7 +46,8 @@ class SampledLogits(object):
 
     def loss(self, mask):
         """SampledCrossEntropyLoss with label 0 and masked mean (tools/lossfunctions.py:36-49)."""
-        return ops.sampled_softmax_loss(self.h, self.table, self.pos, self.negatives(mask), mask, self.k, self.skip_row)
+        return ops.sampled_softmax_loss(self.h, self.table, self.pos, self.negatives(mask), mask, self.k, self.skip_row,
+                                        neg_bias=self.neg_bias, pos_bias=self.pos_bias)
 
     def dense(self):
         """The [B, L, 1 + k] logits tensor the reference's forward returns (AutoEnc4Rec_cross.py:211-215: column 0 the
@@ -50,12 +56,18 @@ class SampledLogits(object):
         from . import hip
         d = self.h.shape[-1]
         h2 = self.h.detach().contiguous().view(-1, d)
-        scores, _ = hip.rank_scores(h2, ops.shadow(self.table), self.pos.contiguous().view(-1),
-                                    self.negatives().contiguous().view(-1, self.k), want_rank=False)
+        neg = self.negatives().contiguous().view(-1, self.k)
+        scores, _ = hip.rank_scores(h2, ops.shadow(self.table), self.pos.contiguous().view(-1), neg, want_rank=False)
+        if self.pos_bias is not None:                      # the logits the corrected loss sees
+            scores[:, 0] += self.pos_bias.reshape(-1).to(torch.float32)
+        if self.neg_bias is not None:
+            scores[:, 1:] += self.neg_bias.to(torch.float32)[neg]
         return scores.view(tuple(self.h.shape[:-1]) + (self.k + 1,))
 
     def bpr(self, mask, sas=False):
         """BPRLoss (tools/lossfunctions.py:56-72); sas=True: BPRLoss_sas (:79-96), what train_auto.py uses (:26)."""
+        if self.neg_bias is not None or self.pos_bias is not None:
+            raise ValueError("BPR is no estimate of a softmax: the logQ correction (neg_bias / pos_bias) serves the sampled softmax only")
         return ops.bpr_loss(self.h, self.table, self.pos, self.negatives(mask), mask, self.k, self.skip_row, sas=sas)
 
 
@@ -63,13 +75,14 @@ class SharedLogits(object):
     """Deferred logits of the positive + ONE candidate list shared by every position of the batch (cand: 1-D, strictly ascending table
     rows).  A candidate equal to a position's own target is left out of that position's softmax."""
 
-    def __init__(self, h, table, labels, cand, skip_row=-1):
+    def __init__(self, h, table, labels, cand, skip_row=-1, cand_bias=None):
         self.h, self.table, self.labels, self.cand, self.skip_row = h, table, labels, cand, skip_row
+        self.cand_bias = cand_bias          # [C] f32 or None: the logQ correction of the list (LogQNegatives; DESIGN.md 6k)
 
     def loss(self, mask):
         """Sampled softmax with label 0 and masked mean over [z_pos, z_cand minus accidental hits] -- the fused kernels of
         csrc/shared_ce.hip, no logits stored."""
-        return ops.shared_softmax_loss(self.h, self.table, self.labels, self.cand, mask, self.skip_row)
+        return ops.shared_softmax_loss(self.h, self.table, self.labels, self.cand, mask, self.skip_row, cand_bias=self.cand_bias)
 
     def dense(self):
         """The [..., 1 + C] f32 logits (column 0 the positive, then the candidates in list order; accidental hits shown as -inf),
@@ -81,6 +94,8 @@ class SharedLogits(object):
         cand = self.cand.contiguous()
         n, C = h2.shape[0], cand.numel()
         out, _ = hip.rank_scores(h2, ops.shadow(self.table), labels, cand.view(1, C).expand(n, C).contiguous(), want_rank=False)
+        if self.cand_bias is not None:
+            out[:, 1:] += self.cand_bias.to(torch.float32).view(1, C)
         out[:, 1:].masked_fill_(cand.view(1, C) == labels.view(n, 1), float("-inf"))
         return out.view(tuple(self.h.shape[:-1]) + (cand.numel() + 1,))
 
@@ -117,10 +132,62 @@ class HardNegatives(object):
         return HardNegatives(mv(self.private), mv(self.pool), self.k_hard, self.skip, mv(self.excl), mv(self.excl_lo), mv(self.excl_hi))
 
 
+class LogQNegatives(object):
+    """A value for the n_items argument: sampled negatives together with the logQ correction of the distribution they were drawn
+    from.  ids 2-D [B, L * k] (per-position draws): neg_bias [table rows] = -log Q per item, pos_bias [B] =
+    log k - log(1 - m_u) per sequence, either may be None.  ids 1-D (one shared candidate list): cand_bias [C] = -log of each
+    candidate's inclusion probability.  The biases are f32 constants: no gradient reaches them."""
+
+    def __init__(self, ids, neg_bias=None, pos_bias=None, cand_bias=None):
+        if not torch.is_tensor(ids) or ids.dtype != torch.int64 or ids.dim() not in (1, 2):
+            raise ValueError("LogQNegatives: ids must be the [B, L * k] int64 draw or a 1-D int64 candidate list")
+        if ids.dim() == 1 and (neg_bias is not None or pos_bias is not None):
+            raise ValueError("LogQNegatives: a 1-D candidate list takes cand_bias, not neg_bias / pos_bias")
+        if ids.dim() == 2 and cand_bias is not None:
+            raise ValueError("LogQNegatives: per-position draws take neg_bias / pos_bias, not cand_bias")
+        if cand_bias is not None and cand_bias.numel() != ids.numel():
+            raise ValueError("LogQNegatives: cand_bias needs one value per candidate (%d, got %d)" % (ids.numel(), cand_bias.numel()))
+        if pos_bias is not None and pos_bias.numel() != ids.shape[0]:
+            raise ValueError("LogQNegatives: pos_bias needs one value per sequence (%d, got %d)" % (ids.shape[0], pos_bias.numel()))
+        for name, b in (("neg_bias", neg_bias), ("pos_bias", pos_bias), ("cand_bias", cand_bias)):
+            if b is not None and (not torch.is_tensor(b) or b.dtype != torch.float32):
+                raise ValueError("LogQNegatives: %s must be an f32 tensor" % name)
+        self.ids, self.neg_bias, self.pos_bias, self.cand_bias = ids, neg_bias, pos_bias, cand_bias
+
+    def dim(self):
+        return self.ids.dim()
+
+    def to(self, device):
+        """The loaders' `n_items.to(device)` (get_next_batch): every tensor moved, shared when already there."""
+        mv = lambda t: None if t is None else t.to(device)
+        return LogQNegatives(mv(self.ids), mv(self.neg_bias), mv(self.pos_bias), mv(self.cand_bias))
+
+
+def sampled_handle(h, table, labels, n_items, k, skip_row=-1):
+    """The deferred-logits handle of a sampled reconstruction loss for any value n_items may take: a 1-D tensor (one shared candidate
+    list), a 2-D tensor or a HardNegatives (per-position negatives), or a LogQNegatives around either tensor form."""
+    if isinstance(n_items, LogQNegatives):
+        if n_items.ids.dim() == 1:
+            return SharedLogits(h, table, labels, n_items.ids, skip_row, cand_bias=n_items.cand_bias)
+        pb = n_items.pos_bias
+        if pb is not None:                                        # one value per sequence -> one per position of labels [B, L]
+            B = n_items.ids.shape[0]
+            if labels.numel() % B != 0:
+                raise ValueError("LogQNegatives: %d sequences of draws for %d labels" % (B, labels.numel()))
+            pb = pb.reshape(-1).repeat_interleave(labels.numel() // B)
+        return SampledLogits(h, table, labels, n_items.ids, k, skip_row, neg_bias=n_items.neg_bias, pos_bias=pb)
+    if torch.is_tensor(n_items) and n_items.dim() == 1:           # one candidate list shared by the batch
+        return SharedLogits(h, table, labels, n_items, skip_row)
+    return SampledLogits(h, table, labels, n_items, k, skip_row)
+
+
 def resolve_negatives(h, table, labels, n_items, k, mask):
     """n_items as the item-loss kernels take it.  A plain tensor passes through untouched.  A HardNegatives becomes a fresh [n, k]
     buffer: the private draw, its first k_hard columns overwritten by each live position's hard negatives of the pool, scored with
     the detached decoder states h against the operand-tier copy of table -- no gradient flows through the selection."""
+    if isinstance(n_items, LogQNegatives):
+        raise ValueError("LogQNegatives serve the sampled reconstruction softmax only (forward(..., recon=True) / the cross model's "
+                         "forward): BPR is no estimate of a softmax")
     if not isinstance(n_items, HardNegatives):
         return n_items
     from . import hip
@@ -324,9 +391,7 @@ class MyAuto4Rec_c(nn.Module):
                 raise ValueError("full-vocabulary logits need projection_%s: construct MyAuto4Rec_c with param.decoder_neg=False "
                                  "(n_negs=%d >= vocab_size_%s=%d)" % (domain, self.param.n_negs, domain, vocab))
             return FullLogits(dec_out, proj.weight, dec_outputs)
-        if torch.is_tensor(n_items) and n_items.dim() == 1:           # one candidate list shared by the batch
-            return SharedLogits(dec_out, self.item_table(domain), dec_outputs, n_items)
-        return SampledLogits(dec_out, self.item_table(domain), dec_outputs, n_items, self.param.n_negs)
+        return sampled_handle(dec_out, self.item_table(domain), dec_outputs, n_items, self.param.n_negs)
 
 
 class MyAuto4Rec(nn.Module):
@@ -395,9 +460,7 @@ class MyAuto4Rec(nn.Module):
         h, _, _ = self.get_dec_out(enc_inputs, dec_inputs)
         if not (self.param.decoder_neg and self.param.n_negs < self.param.vocab_size):
             return FullLogits(h, self.src_emb.weight, dec_outputs)
-        if torch.is_tensor(n_items) and n_items.dim() == 1:           # one candidate list shared by the batch
-            return SharedLogits(h, self.src_emb.weight, dec_outputs, n_items, self.pad_index)
-        return SampledLogits(h, self.src_emb.weight, dec_outputs, n_items, self.param.n_negs, self.pad_index)
+        return sampled_handle(h, self.src_emb.weight, dec_outputs, n_items, self.param.n_negs, self.pad_index)
 
 
 class MyRec(nn.Module):

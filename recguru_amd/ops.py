@@ -1224,8 +1224,19 @@ class DecoderLayerFn(_Fn):
 # K7 / K8: sampled-softmax / BPR loss over the item catalogue
 # ------------------------------------------------------------------------------------------------
 class ItemLoss(_Fn):
+    """neg_bias [table rows] / pos_bias [positions] (f32, no gradient; sampled softmax only): added to the negatives' logits by item id
+    and to the positive's logit -- the logQ correction of DESIGN.md 6k.  They take every route the unbiased loss takes."""
+
     @staticmethod
-    def forward(ctx, h, table, pos, neg, mask, k, mode, skip_row):
+    def forward(ctx, h, table, pos, neg, mask, k, mode, skip_row, neg_bias=None, pos_bias=None):
+        if neg_bias is not None:
+            neg_bias = neg_bias.detach().to(torch.float32).contiguous().view(-1)
+        if pos_bias is not None:
+            pos_bias = pos_bias.detach().to(torch.float32).contiguous().view(-1)
+        bias = dict(neg_bias=neg_bias, pos_bias=pos_bias) if (neg_bias is not None or pos_bias is not None) else {}
+        if bias and mode != hip.LOSS_SAMPLED_CE:
+            raise ValueError("neg_bias / pos_bias (logQ correction) apply to the sampled softmax only, not to a BPR loss")
+        ctx.bias = bias
         d = h.shape[-1]
         h2 = h.contiguous().view(-1, d)
         pos = pos.contiguous().view(-1)
@@ -1251,11 +1262,11 @@ class ItemLoss(_Fn):
                 _DP.global_count(sums[1:2])
             if form == 2:
                 ctx.lse = torch.empty(ntok, device=h2.device, dtype=torch.float32)
-            coef, dh1 = hip.item_loss_train(h2, tab, pos, neg, mask, k, mode, sums, lse=ctx.lse)
+            coef, dh1 = hip.item_loss_train(h2, tab, pos, neg, mask, k, mode, sums, lse=ctx.lse, **bias)
             ctx.save_for_backward(h2, pos, neg, mask, coef, dh1, sums)
             ctx.consumed = False
             return sums[0] / sums[1]
-        sums, aux = hip.item_loss_fwd(h2, tab, pos, neg, mask, k, mode)
+        sums, aux = hip.item_loss_fwd(h2, tab, pos, neg, mask, k, mode, **bias)
         if _DP is not None and _DP.world > 1:
             _DP.global_count(sums[1:2])          # Q12: sum(l*m) / GLOBAL sum(m); grads are SUM-reduced
         ctx.save_for_backward(h2, pos, neg, mask, aux, sums)
@@ -1273,25 +1284,25 @@ class ItemLoss(_Fn):
                 ctx.consumed = True                  # dh1 is scaled in place: it serves ONE backward
                 hip.item_loss_scatter_binned(h2, table.shape[0], pos, neg, mask, k, coef, g1, dE, skip_row,
                                              lse=ctx.lse, sums=sums if ctx.lse is not None else None)
-                return hip.scale_dev(dh1, g1).view(shape), ret, None, None, None, None, None, None
+                return hip.scale_dev(dh1, g1).view(shape), ret, None, None, None, None, None, None, None, None
             # a second backward through a retained graph: the two-call form, from scratch
             cnt = sums[1:2].clone()
-            sums, aux = hip.item_loss_fwd(h2, shadow(table), pos, neg, mask, k, mode)
+            sums, aux = hip.item_loss_fwd(h2, shadow(table), pos, neg, mask, k, mode, **ctx.bias)
             sums[1:2] = cnt
         else:
             h2, pos, neg, mask, aux, sums = ctx.saved_tensors
         fn = hip.item_loss_bwd_binned if ctx.binned else hip.item_loss_bwd
-        dh = fn(h2, shadow(table), pos, neg, mask, k, mode, aux, sums, g1, dE, skip_row)
-        return dh.view(shape), ret, None, None, None, None, None, None
+        dh = fn(h2, shadow(table), pos, neg, mask, k, mode, aux, sums, g1, dE, skip_row, **ctx.bias)
+        return dh.view(shape), ret, None, None, None, None, None, None, None, None
 
 
-def sampled_softmax_loss(h, table, pos, neg, mask, k, skip_row=-1):
-    return ItemLoss.run(h, table, pos, neg, mask, k, hip.LOSS_SAMPLED_CE, skip_row)
+def sampled_softmax_loss(h, table, pos, neg, mask, k, skip_row=-1, neg_bias=None, pos_bias=None):
+    return ItemLoss.run(h, table, pos, neg, mask, k, hip.LOSS_SAMPLED_CE, skip_row, neg_bias, pos_bias)
 
 
-def bpr_loss(h, table, pos, neg, mask, k, skip_row=-1, sas=False):
-    """BPRLoss, or with sas=True BPRLoss_sas (tools/lossfunctions.py:56-72 / :79-96)."""
-    return ItemLoss.run(h, table, pos, neg, mask, k, hip.LOSS_BPR_SAS if sas else hip.LOSS_BPR, skip_row)
+def bpr_loss(h, table, pos, neg, mask, k, skip_row=-1, sas=False, neg_bias=None, pos_bias=None):
+    """BPRLoss, or with sas=True BPRLoss_sas (tools/lossfunctions.py:56-72 / :79-96).  A bias raises: BPR estimates no softmax."""
+    return ItemLoss.run(h, table, pos, neg, mask, k, hip.LOSS_BPR_SAS if sas else hip.LOSS_BPR, skip_row, neg_bias, pos_bias)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -79,19 +79,75 @@ class DeviceDomain(object):
         t = lambda a: torch.as_tensor(a).to(device)
         self.V, self.n, self.device = int(V), n, device
         self.items, self.offsets = t(items), t(off)
-        self.excl, self.excl_off = t(np.concatenate(ex) if n else np.zeros(0, np.int64)), t(exoff)
+        exc = np.concatenate(ex) if n else np.zeros(0, np.int64)
+        self.excl, self.excl_off = t(exc), t(exoff)
         self.val, self.test = t(np.asarray(val, dtype=np.int64)), t(np.asarray(test, dtype=np.int64))
         self.alias = None
         self._no_excl = None
+        self._w = None                                       # the draw's weights (float64, host), kept for the logQ tables
+        self._host_excl = (exc, exoff)
+        self._logq = None
+        self._inclusion = {}
         if wf is not None:                                   # data_loader.py:251-254
             w = np.power(np.asarray(wf, dtype=np.float64), 0.75)
             w[0] = 0.0
             prob, al = alias_table(w / w.sum())
             self.alias = (t(prob), t(al))
+            self._w = w
 
-    def batch(self, users, L_enc, L_dec, eos, n_neg, seed, shared_negs=0, hard_negs=0, hard_k=None, hard_skip=0):
+    # ---- logQ correction of the sampled softmax: host tables in float64, built on first use ----
+    def _q(self):
+        """(Q, Qf) over the rows 0 .. V + 1 of the item table: Q the draw's distribution (w / sum w over 1..V, or 1 / V without
+        frequencies; 0 at row 0, the EOS row and zero-frequency ids), Qf the same with every zero of 1..V raised to the smallest
+        positive Q -- such ids can be labels and the sampler's uniform fall-back can draw them, and a bias has to be finite."""
+        V = self.V
+        Q = np.zeros(V + 2, dtype=np.float64)
+        if self._w is None:
+            Q[1:V + 1] = 1.0 / V
+        else:
+            m = min(len(self._w), V + 1)
+            Q[1:m] = self._w[1:m]
+            Q /= Q.sum()
+        Qf = Q.copy()
+        body = Qf[1:V + 1]
+        body[body <= 0.0] = body[body > 0.0].min()
+        return Q, Qf
+
+    def logq_tables(self):
+        """(neg_bias [V + 2] f32, m_u [users] f64 host, pos_shift [users] f32): -log Qf per table row (0 at row 0 and the EOS row);
+        each user's exclusion mass m_u = sum of Q over its exclusion row; and -log(1 - m_u), the part of pos_bias that does not
+        depend on k (1 - m_u no smaller than the smallest positive Q, so that it stays finite)."""
+        if self._logq is None:
+            Q, Qf = self._q()
+            V = self.V
+            nb = np.zeros(V + 2, dtype=np.float64)
+            nb[1:V + 1] = -np.log(Qf[1:V + 1])
+            exc, exoff = self._host_excl
+            run = np.concatenate([np.zeros(1), np.cumsum(Q[exc])])
+            m_u = run[exoff[1:]] - run[exoff[:-1]]
+            shift = -np.log(np.maximum(1.0 - m_u, Qf[1:V + 1].min()))
+            t = lambda a: torch.as_tensor(a.astype(np.float32)).to(self.device)
+            self._logq = (t(nb), m_u, t(shift))
+        return self._logq
+
+    def inclusion_bias(self, n):
+        """[V + 2] f32, cached per n: -log of the probability that a row is among n independent draws from Qf,
+        -log(1 - (1 - Qf)^n) -- the Horvitz-Thompson weight of a member of shared_candidates(n) (0 at row 0 and the EOS row)."""
+        n = int(n)
+        if n not in self._inclusion:
+            _, Qf = self._q()
+            V = self.V
+            b = np.zeros(V + 2, dtype=np.float64)
+            with np.errstate(divide="ignore"):
+                b[1:V + 1] = -np.log(-np.expm1(n * np.log1p(-Qf[1:V + 1])))
+            self._inclusion[n] = torch.as_tensor(b.astype(np.float32)).to(self.device)
+        return self._inclusion[n]
+
+    def batch(self, users, L_enc, L_dec, eos, n_neg, seed, shared_negs=0, hard_negs=0, hard_k=None, hard_skip=0, logq=False):
         if shared_negs > 0 and hard_negs > 0:
             raise ValueError("hard_negs and shared_negs exclude each other: a shared list has no per-position negatives to harden")
+        if logq and hard_negs > 0:
+            raise ValueError("logq and hard_negs exclude each other: hard columns are not draws from the sampler's distribution")
         users = users.to(self.device).contiguous()
         seqs = hip.assemble_batch(self.items, self.offsets, users, L_enc, L_dec, eos)
         if shared_negs > 0:
@@ -106,6 +162,13 @@ class DeviceDomain(object):
             pool = self.shared_candidates(hard_negs, seed ^ HARD_POOL_SEED)
             n_items = HardNegatives(n_items, pool, k if not hard_k else int(hard_k), hard_skip, excl=self.excl,
                                     excl_lo=self.excl_off[users], excl_hi=self.excl_off[users + 1])
+        if logq:
+            from .models import LogQNegatives
+            if shared_negs > 0:
+                n_items = LogQNegatives(n_items, cand_bias=self.inclusion_bias(shared_negs)[n_items])
+            else:
+                neg_bias, _, shift = self.logq_tables()
+                n_items = LogQNegatives(n_items, neg_bias=neg_bias, pos_bias=shift[users] + float(np.log(n_neg // L_dec)))
         return seqs, n_items, self.val[users], self.test[users]
 
     def shared_candidates(self, n, seed):
@@ -125,15 +188,22 @@ class DeviceLoader(object):
     shared_negs > 0: n_items is ONE 1-D ascending list of the distinct ids among shared_negs draws, shared by the batch, instead of
     the [B, n_neg] per-user draws (every rank draws its own: the batch seed carries the rank).
     hard_negs > 0: n_items is a models.HardNegatives -- the per-user draws plus one pool of the distinct ids among hard_negs draws,
-    from which the model's current top scorers replace the first hard_k (None: all) negatives of every position."""
+    from which the model's current top scorers replace the first hard_k (None: all) negatives of every position.
+    logq=True: n_items is a models.LogQNegatives -- the same draws (or the same shared list) together with the logQ correction of the
+    distribution they came from (DESIGN.md 6k), k = n_neg // L_dec negatives per position."""
 
     def __init__(self, domain, batch_size, L_enc, L_dec, eos, n_neg, seed=0, shuffle=True, rank=0, world=1, drop_last=True,
-                 shared_negs=0, hard_negs=0, hard_k=None, hard_skip=0):
+                 shared_negs=0, hard_negs=0, hard_k=None, hard_skip=0, logq=False):
         self.dom, self.bs, self.Le, self.Ld, self.eos, self.n_neg = domain, batch_size, L_enc, L_dec, eos, n_neg
         self.shared_negs = int(shared_negs)
         self.hard = (int(hard_negs), hard_k, int(hard_skip))
+        self.logq = bool(logq)
         if self.shared_negs > 0 and self.hard[0] > 0:
             raise ValueError("hard_negs and shared_negs exclude each other: a shared list has no per-position negatives to harden")
+        if self.logq and self.hard[0] > 0:
+            raise ValueError("logq and hard_negs exclude each other: hard columns are not draws from the sampler's distribution")
+        if self.logq and self.shared_negs <= 0 and n_neg // L_dec < 1:
+            raise ValueError("logq: fewer than one negative per position (n_neg=%d, L_dec=%d)" % (n_neg, L_dec))
         self.users = torch.arange(rank, domain.n, world, device=domain.device)[:max(domain.n // world, 1 if world == 1 else 0)]   # equal shards (dist.shard_users)
         self.shuffle, self.seed, self.epoch, self.drop_last = shuffle, int(seed) * 1000003 + rank, 0, drop_last
         self.seed_rank = (int(seed), int(rank))
@@ -156,6 +226,8 @@ class DeviceLoader(object):
             seed = batch_seed(self.seed_rank[0], self.seed_rank[1], self.epoch * self.nb + i)
             if self.hard[0] > 0:
                 yield self.dom.batch(u, self.Le, self.Ld, self.eos, self.n_neg, seed, 0, *self.hard)
+            elif self.logq:
+                yield self.dom.batch(u, self.Le, self.Ld, self.eos, self.n_neg, seed, self.shared_negs, logq=True)
             elif self.shared_negs > 0:
                 yield self.dom.batch(u, self.Le, self.Ld, self.eos, self.n_neg, seed, self.shared_negs)
             else:

@@ -55,6 +55,10 @@ def parse():
                         "and train every position against the pool members it ranks highest (both loaders); 0 = off")
     p.add_argument("--hard_k", type=int, default=0, help="--hard_negs: how many of a position's negatives are hard ones (0 = all)")
     p.add_argument("--hard_skip", type=int, default=0, help="--hard_negs: ranks dropped from the head of the pool's order")
+    p.add_argument("--logq", type=lambda v: v == "True", default=False,
+                   help="True: logQ correction of the sampled reconstruction loss (DESIGN.md 6k) -- every negative's logit gets -log of "
+                        "its draw probability (with --shared_negs: of its probability to be on the list), so that the loss estimates the "
+                        "softmax over the catalogue; the BPR phases are unchanged")
     p.add_argument("--pos_train", type=lambda v: v == "True", default=False,
                    help="True: learned positional table of enc_maxlen rows (the reference's pos_train) instead of the fixed sinusoid")
     p.add_argument("--weight_decay", type=float, default=0.0, help="weight decay of both optimizers (recguru_amd/optim.py); 0 = off, as the reference")
@@ -98,15 +102,16 @@ def main():
     L, V = param.enc_maxlen, param.vocab_size - 1
     hard = config.hard_negs_options(param)
     hard_of = lambda kk: config.hard_negs_options(param, kk)                # (a --hard_k above a phase's k: all of that phase's)
+    logq = config.logq_options(param)                                       # pre-training loader only
     item_fre = None
     if args.synthetic:
         ae = synthetic.TensorLoader(synthetic.make_domain(args.synthetic, V, L, param.n_negs, seed=1), param.batch_size, device)
         re = synthetic.TensorLoader(synthetic.make_domain(args.synthetic, V, L, param.num_train_neg, seed=2), param.batch_size, device)
         re_f = re
         seqs, val, test, _ = synthetic.make_users(args.synthetic, V, L, seed=1)
-        if param.shared_negs > 0:                                              # the pre-training loader draws on the device: one list per batch
+        if param.shared_negs > 0 or logq:                                      # the pre-training loader draws on the device: one list per batch, or
             ae = sampler.DeviceLoader(sampler.DeviceDomain(seqs, val, test, V, device), param.batch_size, L, L, V + 1, L * param.n_negs,
-                                      seed=1, shared_negs=param.shared_negs)
+                                      seed=1, shared_negs=param.shared_negs, **logq)      # draws with their logQ tables (the pre-staged loader has none)
         if hard:                                                               # every training loader draws on the device: the draws plus one scored pool per batch
             mk_hard = lambda kk, seed, L_dec: sampler.DeviceLoader(sampler.DeviceDomain(seqs, val, test, V, device), param.batch_size, L, L_dec,
                                                                    V + 1, L_dec * kk, seed=seed, **hard_of(kk))
@@ -122,7 +127,7 @@ def main():
             item_fre = data.load_pickle(found["freq_a"][0])                 # train_auto.py:411-414
         param.vocab_size_a = param.vocab_size
         gen = lambda n, seed, **kw: data.device_loader_gen(files, param, n, "a", device, seed=seed, **kw)
-        ae = gen(param.n_negs, 1, shared_negs=param.shared_negs, **hard_of(param.n_negs))    # train_auto.py:417-430
+        ae = gen(param.n_negs, 1, shared_negs=param.shared_negs, **hard_of(param.n_negs), **logq)    # train_auto.py:417-430
         re = gen(param.n_bpr_neg, 2, rec=True, **hard_of(param.n_bpr_neg))
         re_f = gen(param.n_bpr_neg, 3, rec=True, wf=item_fre, **hard_of(param.n_bpr_neg))
         ev = data.eval_loader_gen(files, param, "a", device, wf=item_fre)

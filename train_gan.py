@@ -66,6 +66,10 @@ def parse():
                         "loaders); 0 = off")
     p.add_argument("--hard_k", type=int, default=0, help="--hard_negs: how many of a position's negatives are hard ones (0 = all)")
     p.add_argument("--hard_skip", type=int, default=0, help="--hard_negs: ranks dropped from the head of the pool's order")
+    p.add_argument("--logq", type=str2bool_par, default=False,
+                   help="True: logQ correction of the sampled reconstruction loss (DESIGN.md 6k) -- every negative's logit gets -log of "
+                        "its draw probability (with --shared_negs: of its probability to be on the list), so that the loss estimates the "
+                        "softmax over the catalogue; the BPR phases are unchanged")
     p.add_argument("--pos_train", type=str2bool_par, default=False,
                    help="True: learned positional tables of enc_maxlen rows for both domains instead of the fixed sinusoid "
                         "(this project's extension of the cross model)")
@@ -114,18 +118,19 @@ def main():
     L, k = param.enc_maxlen, param.n_negs
     hard = param_c.hard_negs_options(param)
     hard_of = lambda kk: param_c.hard_negs_options(param, kk)          # (a --hard_k above a phase's k: all of that phase's)
+    logq = param_c.logq_options(param)                                 # reconstruction loaders only
     if args.synthetic:
         dom_a = synthetic.make_domain(args.synthetic, param.vocab_size_a - 1, L, k, seed=1)
         dom_b = synthetic.make_domain(args.synthetic, param.vocab_size_b - 1, L, k, seed=2)
         mk = lambda dom: synthetic.TensorLoader(dom, param.batch_size, device, rank, world)
         ae_loaders = [mk(dom_a), mk(dom_b)]
-        if param.shared_negs > 0:                                  # the reconstruction loaders draw on the device: one list per batch
-            from recguru_amd import sampler
+        if param.shared_negs > 0 or logq:                          # the reconstruction loaders draw on the device: one list per batch, or
+            from recguru_amd import sampler                        # draws that come with their logQ tables (the pre-staged loader has none)
 
             def mk_shared(V, seed):
                 seqs, val, test, _ = synthetic.make_users(args.synthetic, V, L, seed=seed)
                 return sampler.DeviceLoader(sampler.DeviceDomain(seqs, val, test, V, device), param.batch_size, L, L, V + 1, L * k,
-                                            seed=10 + seed, rank=rank, world=world, shared_negs=param.shared_negs)
+                                            seed=10 + seed, rank=rank, world=world, shared_negs=param.shared_negs, **logq)
             ae_loaders = [mk_shared(param.vocab_size_a - 1, 1), mk_shared(param.vocab_size_b - 1, 2)]
         rec_dom = synthetic.make_domain(args.synthetic, (param.vocab_size_a if args.target_domain == "a"
                                                          else param.vocab_size_b) - 1, L, param.n_bpr_neg, seed=3)
@@ -160,8 +165,8 @@ def main():
                 sys.exit("train_gan.py: no '%s' pickle under %s (train_gan.py:65-79 naming)" % (need, param.data_path))
         # shuffled loaders with FRESH negatives per batch (data_loader.py:276-316,455-483), on the device
         gen = lambda f, n, dom, seed, **kw: Dataloader.device_loader_gen(f, param, n, dom, device, rank, world, seed=seed, **kw)
-        ae_loaders = [gen(files["a"], k, "a", 11, shared_negs=param.shared_negs, **hard_of(k)),
-                      gen(files["b"], k, "b", 12, shared_negs=param.shared_negs, **hard_of(k))]
+        ae_loaders = [gen(files["a"], k, "a", 11, shared_negs=param.shared_negs, **hard_of(k), **logq),
+                      gen(files["b"], k, "b", 12, shared_negs=param.shared_negs, **hard_of(k), **logq)]
         freq = Dataloader.load_pickle(files["freq_" + t][0])
         rec_loaders = [gen(files[t], param.n_bpr_neg, t, 13, rec=True, **hard_of(param.n_bpr_neg)),
                        gen(files[t], param.n_bpr_neg, t, 14, rec=True, wf=freq, **hard_of(param.n_bpr_neg))]
